@@ -8,7 +8,11 @@ GPT1.py:227-233 (get_batch, forward, zero_grad, backward, [grad all-reduce], opt
 replayed from a hipGraph.  N > 1 GPUs: data parallel, weak scaling (64 sequences per GPU),
 bucketed RCCL all-reduce of the fp32 gradient buffer.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times ``--steps`` steps, writes the last step's outputs when
+``--dump-outputs DIR`` is given, and prints ONE JSON line on rank 0.  ``--full`` adds everything else
+the benchmark measures after the timed region: the GEMM / kernel census with the roofline figures
+and the in-step probe, the C5 batched decode and the CPU baseline (each can be left out of a full
+run with its ``--no-...`` option).
 """
 import argparse
 import json
@@ -660,6 +664,29 @@ def dry_run(args, world, rank, local):
         dist.destroy_process_group()
 
 
+DUMP_MAX_ELEMS = 7 << 20   # per array: two fp32 arrays of this size and the loss stay under 64 MB
+
+
+def dump_outputs(out_dir, loss, model):
+    """What a caller of the timed step holds after its last step, as float32 ``<name>.npy`` files:
+    the step's mean loss, and the model's flat fp32 parameters (after the step's AdamW update) and
+    gradients (of the step's backward).  A flat buffer above DUMP_MAX_ELEMS elements is written as a
+    fixed sample: the elements at sorted offsets drawn once from a private generator (seed 1337), the
+    same offsets in every run of the same configuration."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    flat = model.flat
+    ix = None
+    if flat.numel > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(1337)
+        ix = torch.randint(flat.numel, (DUMP_MAX_ELEMS,), generator=g).sort().values.to(flat.master.device)
+    for name, t in (("params", flat.master), ("grads", flat.grad)):
+        t = t.detach()
+        np.save(os.path.join(out_dir, name + ".npy"), (t if ix is None else t[ix]).float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -668,9 +695,14 @@ def main():
     ap.add_argument("--config", default="c2", choices=["c2", "c4", "c1"])
     ap.add_argument("--batch", type=int, default=None, help="sequences per GPU (default: config)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-census", action="store_true")
-    ap.add_argument("--no-generate", action="store_true", help="skip the C5 batched-decode measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the GEMM / kernel census with the roofline figures and the "
+                         "in-step probe, the C5 batched decode and the CPU baseline (off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-census", action="store_true", help="--full without the census / roofline / in-step probe")
+    ap.add_argument("--no-generate", action="store_true", help="--full without the C5 batched-decode measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, parameters, gradients) as DIR/<name>.npy")
     ap.add_argument("--overlap", type=int, default=None, choices=[0, 1],
                     help="force the segmented (DP-overlap) backward on/off (default: on when N > 1)")
     ap.add_argument("--seg-layers", type=int, default=2,
@@ -740,6 +772,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     final_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
     tokens = world * Bsz * T * args.steps
     value = tokens / elapsed
     ms_step = elapsed / args.steps * 1e3
@@ -757,7 +791,7 @@ def main():
     torch.cuda.empty_cache()
     if rank == 0:
         roofline, census = None, None
-        if not args.no_census:
+        if args.full and not args.no_census:
             census = gemm_census(cfg, Bsz, T, dev)
             dom = max(census, key=lambda c: c["ms"] * c["launches"])
             c_ach = dom["flops"] / (dom["ms"] * 1e-3) / 1e12
@@ -808,10 +842,10 @@ def main():
             _log("gemm census done; kernel census")
             result["gemm_census_ms"] = {c["name"]: round(c["ms"], 4) for c in census}
             result["kernel_census"] = kernel_census(cfg, Bsz, T, dev)
-        if world == 1 and not args.no_generate:
+        if args.full and world == 1 and not args.no_generate:
             _log("generate (C5)")
             result["generate_c5"] = bench_generate(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             _log("cpu baseline")
             result["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(result), flush=True)

@@ -21,7 +21,7 @@ def test_bench_dp_two_ranks_on_one_gpu():
     env = dict(os.environ, CHARPT_DP_BACKEND="gloo", CHARPT_DP_ONE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-generate"]
+           "--full", "--no-cpu-baseline", "--no-generate"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -131,7 +131,13 @@ def test_c1_shape_grads_match_reference():
 
 
 def test_train_steps_match_reference_p0():
-    """A few GPT1.py:221-233 iterations with Dropout=0 (CPU RNG only feeds get_batch)."""
+    """A few GPT1.py:221-233 iterations with Dropout=0 (CPU RNG only feeds get_batch).
+
+    The bound is 2e-4 * (i + 1) at the initial loss (4.3), i.e. 4.6e-5 * (i + 1) of the loss, and keeps
+    that relative size where the loss grows: at lr 0.5 it reaches 76 by the third step, and there the
+    same fp32 oracle run lands 3e-4 to 2.6e-3 from the stored figure depending only on how the BLAS
+    splits its sums (thread count, buffer alignment: it varies from run to run on one host), so an
+    absolute 6e-4 held or failed by chance.  At lr 2e-4 the loss only falls and the bound is unchanged."""
     g = torch.load(golden_path("train_c1_p0.pt"), weights_only=True)
     text = open(INPUT, encoding="utf-8").read()
     chars, stoi = O.build_vocab(text)
@@ -148,5 +154,6 @@ def test_train_steps_match_reference_p0():
             ix = O.draw_ix(len(tr), 256, 64)
             x, y = O.windows(tr, ix, 256)
             _, loss, grads = O.loss_and_grads(P, x[:, :], y, cfg)
-            assert abs(float(loss) - float(want[i])) < 2e-4 * (i + 1), (key, i, float(loss), float(want[i]))
+            tol = 2e-4 * (i + 1) * max(1.0, float(want[i]) / float(want[0]))
+            assert abs(float(loss) - float(want[i])) < tol, (key, i, float(loss), float(want[i]))
             opt.step(grads)

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p $R/gpurun_out/prof_$tag
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$tag -o run -- \
-  python3 $R/bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-generate \
+  python3 $R/bench.py --config $cfg --steps 20 --warmup 5 --full --no-cpu-baseline --no-generate \
   > $R/gpurun_out/prof_$tag/bench.json 2> $R/gpurun_out/prof_$tag/bench.err || exit $?
 trace=$(find $R/gpurun_out/prof_$tag -name 'run_kernel_trace.csv' | head -1)
 stats=$(find $R/gpurun_out/prof_$tag -name 'run_kernel_stats.csv' | head -1)

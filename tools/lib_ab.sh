@@ -8,7 +8,7 @@ mkdir -p $R/gpurun_out/ab_$tag
 for r in $(seq 1 $rounds); do
   for v in A B; do
     if [ $v = A ]; then lib=$R/replicatinggpt_amd/libcharpt_hip.so; else lib=$R/replicatinggpt_amd/$libb; fi
-    CHARPT_LIB=$lib timeout -k 10 300 python3 $R/bench.py --config $cfg --steps 30 --warmup 10 --no-cpu-baseline \
+    CHARPT_LIB=$lib timeout -k 10 300 python3 $R/bench.py --config $cfg --steps 30 --warmup 10 --full --no-cpu-baseline \
       --no-generate > $R/gpurun_out/ab_$tag/${v}_$r.json 2> $R/gpurun_out/ab_$tag/${v}_$r.err || exit $?
   done
 done
