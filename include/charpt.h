@@ -238,8 +238,9 @@ int cg_gemm_resid_layernorm(int64_t M, int64_t N, int64_t K, const void* A, int6
    (ldw), resid / out [M][N] (ldr / ldo) -- bit for bit [cg_layernorm_fwd +] cg_gemm (fp32,
    CG_EPI_STORE / CG_EPI_BIAS / CG_EPI_BIAS_RELU / CG_EPI_BIAS_RESID), without the normalised rows in
    memory.  Only where cg_linear_rows_f32_supported(M, N, K) says 1 (K <= 128 even; above 2048 rows
-   N <= 2048 even); lda / ldw even and a / W 8-B aligned; above 2048 rows also ldo / ldr even, out /
-   resid 8-B aligned and, with the LayerNorm, ln_w / ln_b 8-B aligned and lda == K; else CG_EINVAL. */
+   N <= 2048 even); lda / ldw even, a / W 8-B aligned and, with the LayerNorm, ln_w / ln_b 8-B aligned
+   (cg_layernorm_fwd sums a row in this launch's order only then); above 2048 rows also ldo / ldr
+   even, out / resid 8-B aligned and, with the LayerNorm, lda == K; else CG_EINVAL.                */
 int cg_linear_rows_f32_supported(int64_t M, int64_t N, int64_t K);
 int cg_linear_rows_f32(int64_t M, int64_t N, int64_t K, const float* a, int64_t lda, const float* ln_w,
                        const float* ln_b, float eps, const float* w, int64_t ldw, const float* bias, int relu,
@@ -249,7 +250,7 @@ int cg_linear_rows_f32(int64_t M, int64_t N, int64_t K, const float* a, int64_t 
    eps) W^T (x [B][C] (ldx), W [3C][C] (ldw), qkv [B][3C] (ldq)), and columns C..3C-1 of row b also
    to kcache / vcache [B][H][Tmax][C/H] at position *len_dev - 1 -- bit for bit cg_linear_rows_f32
    (with the LayerNorm) then cg_decode_kv_append(qkv, ldq, C, 2C, ...).  B <= 2048, C <= 128 even,
-   H | C, ldx / ldw even, x / W 8-B aligned; else CG_EINVAL.                                      */
+   H | C, ldx / ldw even, x / W / ln_w / ln_b 8-B aligned; else CG_EINVAL.                        */
 int cg_decode_qkv_f32(int64_t B, int64_t C, int64_t H, const float* x, int64_t ldx, const float* ln_w,
                       const float* ln_b, float eps, const float* w, int64_t ldw, float* qkv, int64_t ldq,
                       const int64_t* len_dev, int64_t Tmax, float* kcache, float* vcache, void* stream);
@@ -362,8 +363,9 @@ int cg_decode_kv_append(const float* qkv, int64_t ld, int64_t k_off, int64_t v_o
 int cg_decode_attn(const float* q, int64_t ldq, const float* k, const float* v, int64_t sb, int64_t sh, int64_t sj,
                    int64_t B, int64_t H, int64_t D, const int64_t* len_dev, int64_t nkeys, float scale, float* o,
                    int64_t ldo, void* stream);
-/* idx[b, len] <- argmax(logits[b]) (greedy, first index on ties) or an inverse-CDF draw from
-   softmax(logits[b]) with u from Philox(*seed_dev, stream = len, counter = b)                     */
+/* idx[b, len] <- argmax(logits[b]) (greedy: first index on ties, NaN counts as the maximum --
+   torch.argmax's rules, so always inside [0, V)) or an inverse-CDF draw from softmax(logits[b])
+   with u from Philox(*seed_dev, stream = len, counter = b)                                        */
 int cg_decode_sample(const float* logits, int64_t ldl, int64_t V, int64_t B, int greedy, const uint64_t* seed_dev,
                      const int64_t* len_dev, int64_t* idx, int64_t ld, void* stream);
 

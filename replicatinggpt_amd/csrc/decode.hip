@@ -265,7 +265,14 @@ __global__ __launch_bounds__(64) void k_decode_attn_rows(const float* __restrict
     if (lane < D) o[b * ldo + h * D + lane] = out;
 }
 
-// next token per row from logits [B, V]: greedy = first argmax (torch.argmax tie rule); else
+// (x, v) ahead of (best, bi) in torch.argmax's order: NaN counts as the maximum, the lower index
+// wins among equals (so a row holding NaN yields its first NaN's index, never an index outside [0, V))
+__device__ __forceinline__ bool argmax_ahead(float x, int v, float best, int bi) {
+    if (x != x) return best == best || v < bi;
+    return best == best && (x > best || (x == best && v < bi));
+}
+
+// next token per row from logits [B, V]: greedy = first argmax (torch.argmax tie and NaN rule); else
 // inverse-CDF sampling of softmax(logits) with u = Philox(seed, stream = step)[b] / 2^32.
 // Writes idx[b, len] (len = *len_dev) -- the caller then advances *len_dev.
 __global__ __launch_bounds__(64) void k_decode_sample(const float* __restrict__ logits, int64_t ldl, int64_t V,
@@ -280,13 +287,13 @@ __global__ __launch_bounds__(64) void k_decode_sample(const float* __restrict__ 
     int bi = 0x7fffffff;
     for (int v = lane; v < V; v += 64) {
         const float x = row[v];
-        if (x > best || (x == best && v < bi)) { best = x; bi = v; }
+        if (argmax_ahead(x, v, best, bi)) { best = x; bi = v; }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const float ob = __shfl_xor(best, off, 64);
         const int oi = __shfl_xor(bi, off, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        if (argmax_ahead(ob, oi, best, bi)) { best = ob; bi = oi; }
     }
     const int64_t len = *len_dev;
     int64_t tok = bi;

@@ -1817,6 +1817,10 @@ extern "C" int cg_linear_rows_f32(int64_t M, int64_t N, int64_t K, const float* 
         CG_REQUIRE(lda >= K && lda % 2 == 0 && ldw >= K && ldw % 2 == 0 && ldo >= N && (!resid || ldr >= N),
                    "cg_linear_rows_f32: bad leading dimensions");
         CG_REQUIRE((((uintptr_t)a | (uintptr_t)w) & 7) == 0, "cg_linear_rows_f32: a, w must be 8-B aligned");
+        // (the in-launch LayerNorm is k_ln_fwd's narrow-row body, cg_layernorm_fwd's choice only for 8-B
+        // aligned x / w / b: with other ln_w / ln_b the two launches sum a row in another order)
+        CG_REQUIRE(!ln_w || (((uintptr_t)ln_w | (uintptr_t)ln_b) & 7) == 0,
+                   "cg_linear_rows_f32: ln_w / ln_b must be 8-B aligned");
         EpiArgs e{};
         e.kind = resid ? CG_EPI_BIAS_RESID : relu ? CG_EPI_BIAS_RELU : bias ? CG_EPI_BIAS : CG_EPI_STORE;
         e.bias = bias;
@@ -1889,7 +1893,8 @@ extern "C" int cg_decode_qkv_f32(int64_t B, int64_t C, int64_t H, const float* x
     CG_REQUIRE(x && ln_w && ln_b && w && qkv && len_dev && kcache && vcache, "cg_decode_qkv_f32: null pointer");
     CG_REQUIRE(ldx >= C && ldx % 2 == 0 && ldw >= C && ldw % 2 == 0 && ldq >= 3 * C,
                "cg_decode_qkv_f32: bad leading dimensions");
-    CG_REQUIRE((((uintptr_t)x | (uintptr_t)w) & 7) == 0, "cg_decode_qkv_f32: x, w must be 8-B aligned");
+    CG_REQUIRE((((uintptr_t)x | (uintptr_t)w | (uintptr_t)ln_w | (uintptr_t)ln_b) & 7) == 0,
+               "cg_decode_qkv_f32: x, w, ln_w, ln_b must be 8-B aligned");
     EpiArgs e{};
     e.kind = CG_EPI_STORE;
     const KvAppend kva{kcache, vcache, len_dev, C, H, C / H, Tmax};

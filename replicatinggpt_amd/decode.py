@@ -70,18 +70,19 @@ class DecodeEngine:
         return self._R(key).master
 
     def _ln(self, x2, key):
-        y, _, _ = Fn.layernorm(x2, self._b(key + "_w"), self._b(key + "_b"), self.act)
+        # layernorm_fwd takes no row stride: a row-strided view (the window's final rows) goes in as a dense copy
+        y, _, _ = Fn.layernorm(x2.contiguous(), self._b(key + "_w"), self._b(key + "_b"), self.act)
         return y
 
     def _ln_linear(self, x2, key, w, out, bias=None, relu=False):
         """out = act(LayerNorm_key(x2) @ w^T [+ bias]): fp32 per-token rows in one launch
         (ops.linear_rows_f32, k_gemm_f32r with the LayerNorm in its prologue -- the bits of the two
-        launches); else the LayerNorm launch and the GEMM."""
+        launches); else the LayerNorm launch (on dense rows) and the GEMM.  x2 may be row-strided."""
         lw, lb = self._b(key + "_w"), self._b(key + "_b")
         M, K = x2.shape
         if (DECODE_ROWS and self.act == torch.float32 and M <= 2048 and x2.stride(0) % 2 == 0
                 and ops.linear_rows_f32_supported(M, w.shape[0], K) and w.stride(0) % 2 == 0
-                and ((x2.data_ptr() | w.data_ptr()) & 7) == 0):
+                and ((x2.data_ptr() | w.data_ptr() | lw.data_ptr() | lb.data_ptr()) & 7) == 0):
             ops.linear_rows_f32(x2, lw, lb, 1e-5, w, bias, None, out, relu)
             return
         a = self._ln(x2, key)
@@ -109,11 +110,12 @@ class DecodeEngine:
         for l in range(self.L):
             qkv = torch.empty((B, 3 * C), dtype=self.act, device=self.dev)
             wq = self._w(f"{l}.qkv")
+            lw, lb = self._b(f"{l}.ln1_w"), self._b(f"{l}.ln1_b")
             if (DECODE_ROWS and self.act == torch.float32 and B <= 2048 and C <= 128 and C % 2 == 0
-                    and x.stride(0) % 2 == 0 and wq.stride(0) % 2 == 0 and ((x.data_ptr() | wq.data_ptr()) & 7) == 0):
+                    and x.stride(0) % 2 == 0 and wq.stride(0) % 2 == 0
+                    and ((x.data_ptr() | wq.data_ptr() | lw.data_ptr() | lb.data_ptr()) & 7) == 0):
                 # ln1 + QKV + the K / V append in one launch
-                ops.decode_qkv_f32(x, self._b(f"{l}.ln1_w"), self._b(f"{l}.ln1_b"), 1e-5, wq, qkv, self.len,
-                                   self.kc[l], self.vc[l])
+                ops.decode_qkv_f32(x, lw, lb, 1e-5, wq, qkv, self.len, self.kc[l], self.vc[l])
                 qkv32 = qkv
             else:
                 self._ln_linear(x, f"{l}.ln1", wq, qkv)

@@ -90,8 +90,14 @@ def embed_bwd_workspace(B, T, C, V):
 # ---------------------------------------------------------------------------------------
 @_op("layernorm_fwd", ("y", "mean", "rstd"))
 def layernorm_fwd(x: Tensor, w: Tensor, b: Tensor, y: Tensor, mean: Tensor, rstd: Tensor, eps: float) -> None:
+    """y = LayerNorm(x; w, b, eps) over the last dim, mean / rstd per row.  cg_layernorm_fwd takes
+    pointers and no row stride: x and y must be dense (contiguous) -- a row-strided view raises instead
+    of having the wrong rows normalised."""
     C = x.shape[-1]
     rows = x.numel() // C
+    if not x.is_contiguous() or not y.is_contiguous():
+        raise ValueError(f"layernorm_fwd: x and y must be dense (x strides {tuple(x.stride())}, y strides "
+                         f"{tuple(y.stride())}): pass x.contiguous()")
     L.check(L.load().cg_layernorm_fwd(L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y), L.dtype_code(y.dtype), L.ptr(mean),
                                       L.ptr(rstd), rows, C, eps, _s(x)), "layernorm_fwd")
 
@@ -246,8 +252,9 @@ def linear_rows_f32(a: Tensor, ln_w: Optional[Tensor], ln_b: Optional[Tensor], e
                     bias: Optional[Tensor], resid: Optional[Tensor], out: Tensor, relu: bool = False) -> None:
     """out = [resid +] act(a' @ w^T [+ bias]), a' = LayerNorm(a; ln_w, ln_b, eps) (or a when ln_w is None),
     act = relu when relu (bias, no resid), fp32, K <= 128, one launch -- the bits of [layernorm_fwd +]
-    gemm(..., "store" / "bias" / "bias_relu" / "bias_resid").  Fails (CG_EINVAL) unless
-    linear_rows_f32_supported(M, N, K)."""
+    gemm(..., "store" / "bias" / "bias_relu" / "bias_resid").  a may be row-strided (even stride), w a
+    row slice, out / resid column slices.  Fails (CG_EINVAL) unless linear_rows_f32_supported(M, N, K),
+    a / w and, with the LayerNorm, ln_w / ln_b 8-B aligned."""
     M, K = a.shape
     N = w.shape[0]
     for t, name in ((a, "a"), (w, "w"), (bias, "bias"), (resid, "resid"), (out, "out"), (ln_w, "ln_w"),
@@ -448,7 +455,8 @@ def decode_kv_append(qkv: Tensor, k_off: int, v_off: int, len_dev: Tensor, kcach
 def decode_qkv_f32(x: Tensor, ln_w: Tensor, ln_b: Tensor, eps: float, w: Tensor, qkv: Tensor, len_dev: Tensor,
                    kcache: Tensor, vcache: Tensor) -> None:
     """qkv = LayerNorm(x) @ w^T and its K / V columns appended to the caches at position len - 1, fp32,
-    one launch -- the bits of linear_rows_f32(x, ln_w, ln_b, eps, w, ...) then decode_kv_append."""
+    one launch -- the bits of linear_rows_f32(x, ln_w, ln_b, eps, w, ...) then decode_kv_append.  Fails
+    (CG_EINVAL) unless x / w / ln_w / ln_b are 8-B aligned."""
     B, C = x.shape
     _, H, Tmax, D = kcache.shape
     for t, name in ((x, "x"), (w, "w"), (qkv, "qkv"), (kcache, "kcache"), (vcache, "vcache")):
