@@ -6,6 +6,8 @@
 #include "common.h"
 
 namespace cg {
+extern int g_adamw_mode;   // cg_set_tuning("adamw_mode", 0..5): cg_adamw's kernel form, 0 = by size (ce_adamw.hip)
+
 // The fp32 arithmetic of torch/optim/adam.py _single_tensor_adam (decoupled decay) as torch's CPU
 // kernels round it:
 //   p *= 1 - lr*wd ; m = fma(1-b1, g - m, m) [lerp, w < 0.5: the vectorised CPU lerp fuses] ;

@@ -64,6 +64,8 @@ void launch_dkdv_d64(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t*
                      const bf16_t* dout, int64_t ldd, const float* lse, const float* delta, bf16_t* dk, bf16_t* dv,
                      int64_t lddkv, float scale, const DropArgs& d, hipStream_t st);
 }  // namespace attn
+// cg_set_tuning knobs (attention_d64.hip)
 extern int g_attn_variant;
+extern int g_attn_bwd_lpt;
 
 }  // namespace cg

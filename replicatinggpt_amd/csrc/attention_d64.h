@@ -29,8 +29,6 @@
 #include "attention_common.h"
 
 namespace cg {
-extern int g_attn_variant;
-extern int g_attn_bwd_lpt;
 
 #ifdef CG_ATTN_STAMPS
 // Diagnostic build only (make attnstamps; tools/attn_stamps.py): per workgroup of the resident

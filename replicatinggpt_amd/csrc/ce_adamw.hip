@@ -4,7 +4,7 @@
 
 #include "adamw.h"
 #include "common.h"
-#include "gemm_common.h"
+#include "defer.h"
 
 using namespace cg;
 
@@ -227,12 +227,6 @@ __global__ __launch_bounds__(256) void k_adamw_segs(float* __restrict__ p, const
         *(float4*)(v + i) = vv;
         if (pb) *(uint2*)(pb + i) = make_uint2(pack_bf2(pv.x, pv.y), pack_bf2(pv.z, pv.w));
     }
-}
-
-namespace cg {
-int adamw_segments_launch(float* p, const float* g, float* m, float* v, bf16_t* pb, const int64_t* segs, int nseg,
-                          double lr, double beta1, double beta2, double eps, double wd, const int64_t* step,
-                          hipStream_t st);
 }
 
 extern "C" int cg_adamw_segments(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, const int64_t* segs,

@@ -13,8 +13,9 @@
 // ---------------------------------------------------------------------------------------
 namespace cg {
 void set_error(const char* fmt, ...);
+extern int g_decode_attn_rows;   // cg_set_tuning("decode_attn_rows", 0 / 1): decode.hip, which has no header
 // out[n] (=|+=) sum_k part[k*N + n] in a fixed order (deterministic); columns n >= S go to
-// out_b[n - S] (either output may be NULL to drop it).  Defined in util.hip.
+// out_b[n - S] (either output may be NULL to drop it).  Defined in reduce.hip.
 void launch_reduce_partials(const float* part, int64_t K, int64_t N, float* out_a, float* out_b, int64_t S,
                             int accumulate, hipStream_t st);
 // three segments of S columns: out_a, out_b (accumulate), out_c (accumulate_c)

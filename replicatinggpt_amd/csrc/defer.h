@@ -43,11 +43,25 @@ std::mutex& defer_mutex();
 DeferQueue* defer_queue(hipStream_t st, bool create);
 // remove an emptied queue from the registry (q is invalid afterwards)
 void defer_queue_drop(DeferQueue* q);
-// queued column-sum reduces whose outputs overlap [p, p + n) go out now (util.hip)
+// queued column-sum reduces whose outputs overlap [p, p + n) go out now
 void flush_parts_touching_locked(DeferQueue* q, const float* p, int64_t n);
 // launch (on the queue's stream) and clear one kind of job
 void flush_red_locked(DeferQueue& q);
 void flush_adam_locked(DeferQueue& q);
-void flush_parts_locked(DeferQueue& q);   // util.hip
+void flush_parts_locked(DeferQueue& q);
+// queue one column-sum reduce on stream st (takes the lock itself)
+void enqueue_partials(const PartJob& j, hipStream_t st);
+
+// defer.hip holds host code only; the kernels its flushes launch:
+void launch_reduce_partials_multi(const PartJobs& jobs, hipStream_t st);   // reduce.hip
+int adamw_job_launch(const AdamJob& j, hipStream_t st);                    // ce_adamw.hip
+int adamw_segments_launch(float* p, const float* g, float* m, float* v, bf16_t* pb, const int64_t* segs, int nseg,
+                          double lr, double beta1, double beta2, double eps, double wd, const int64_t* step,
+                          hipStream_t st);                                 // ce_adamw.hip
+
+// cg_set_tuning knobs (defer.hip; g_red_side is with take_pending_reduces in gemm_common.h)
+extern int g_adam_per_launch;      // AdamW jobs one launch's free blocks take (0 = MAX_ADAM)
+extern int g_adam_batch;           // A/B build only: the side blocks' AdamW chunks in flight per thread
+extern int g_skip_splitk_reduce;   // measurement knob (WRONG results): time a step without the split-K reduce
 
 }  // namespace cg

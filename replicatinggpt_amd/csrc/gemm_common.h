@@ -1,9 +1,14 @@
-// charpt GEMM internals shared by gemm.hip (generic path, dispatch) and gemm_bf16.hip (MFMA path).
+// charpt GEMM internals shared by gemm.hip (generic path, dispatch), gemm_f32.hip / rows_f32.hip (the fp32
+// MFMA and row kernels), reduce.hip (split-K reduces) and gemm_bf16.hip (MFMA path).
 #pragma once
+#include <type_traits>
+
 #include "adamw.h"
 #include "common.h"
 
 namespace cg {
+
+typedef float fv16f __attribute__((ext_vector_type(16)));   // a 32x32 MFMA accumulator
 
 struct EpiArgs {
     int kind;
@@ -76,6 +81,51 @@ __device__ __forceinline__ void store_out(TC* C, int64_t off, float v, float bet
     st_from_f32<TC>(C + off, v);
 }
 
+// the epilogue kinds the fp32 forward kernels (gemm_f32.hip, rows_f32.hip) specialise, all at beta 0
+inline bool f32_epi_kind(int kind) {
+    return kind == CG_EPI_STORE || kind == CG_EPI_BIAS || kind == CG_EPI_BIAS_RELU || kind == CG_EPI_BIAS_RESID;
+}
+// host dispatch on those four kinds: f(std::integral_constant<int, EK>{}) for a kind that f32_epi_kind accepts
+template <typename F>
+inline void with_epi_kind(int kind, F&& f) {
+    switch (kind) {
+        case CG_EPI_STORE: f(std::integral_constant<int, CG_EPI_STORE>{}); break;
+        case CG_EPI_BIAS: f(std::integral_constant<int, CG_EPI_BIAS>{}); break;
+        case CG_EPI_BIAS_RELU: f(std::integral_constant<int, CG_EPI_BIAS_RELU>{}); break;
+        default: f(std::integral_constant<int, CG_EPI_BIAS_RESID>{}); break;
+    }
+}
+// the same doubled by a flag (the in-launch LayerNorm): f(kind constant, std::bool_constant<flag>{})
+template <typename F>
+inline void with_epi_kind(int kind, bool flag, F&& f) {
+    with_epi_kind(kind, [&](auto ek) {
+        if (flag) f(ek, std::true_type{});
+        else f(ek, std::false_type{});
+    });
+}
+
+// gemm_f32.hip: cg_gemm's fp32 MFMA products (any layout and split; picks among its kernels)
+void launch_f32(int a_trans, int b_trans, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
+                const float* B, int64_t ldb, float* C, int64_t ldc, const EpiArgs& e, int split_k, float* ws,
+                hipStream_t st);
+// k_gemm_f32r's K / V append (generate()'s per-token QKV product): columns C..3C-1 of each row also go to
+// the layer's K / V caches [rows][H][Tmax][D] at position *len - 1
+struct KvAppend {
+    float* kc;
+    float* vc;
+    const int64_t* len;
+    int64_t C, H, D, Tmax;
+};
+// gemm_f32.hip: the K-resident small-M forward (M <= 2048, K even with ceil16(K) <= 624; with ln_w / ln_b
+// or kv K <= 128); the caller checks the conditions
+void launch_f32r(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+                 int64_t ldc, const EpiArgs& e, const float* ln_w, const float* ln_b, float eps, const KvAppend* kv,
+                 hipStream_t st);
+// reduce.hip: C = epilogue(sum of the S split-K slabs in ws, k = 0..S-1 in order); vec4: the four-column
+// form applies (N % 4 == 0, 16-B aligned rows, M N < 2^31) -- every form gives the same bits
+void launch_splitk_reduce(const void* ws, int S, int64_t M, int64_t N, void* C, int c_dtype, int64_t ldc,
+                          const EpiArgs& e, bool vec4, hipStream_t st);
+
 
 // A split-K reduce deferred out of its own cg_gemm call (CG_GEMM_DEFER_REDUCE, the training
 // backward; queued per stream, defer.h): out[i] = sum_{s < S} ws[s n + i] (+ beta out[i]) over n = 4 n4 fp32 elements,
@@ -113,11 +163,13 @@ struct RedJobs {
     int na;   // AdamW jobs: only a launch with free blocks (red_tail `first` > 0) is given any
     int adam_batch;   // A/B build only (cg_set_tuning "adam_batch"): chunks in flight per thread (1 = product loop)
 };
-// gemm.hip: pending jobs (cleared) for a launch on st -- the split-K reduces, and with side_ok (the
+// defer.hip: pending jobs (cleared) for a launch on st -- the split-K reduces, and with side_ok (the
 // launch has >= SIDE_MIN free blocks) the AdamW jobs; has_pending_reduces: whether it would take any
 constexpr int SIDE_MIN = 64;
 RedJobs take_pending_reduces(hipStream_t st, bool side_ok = false);
 bool has_pending_reduces(hipStream_t st, bool side_ok = false);
+// cg_set_tuning("red_side", v): a part-filling persistent launch takes a pending reduce on extra blocks (defer.hip)
+extern int g_red_side;
 
 // out[8i .. 8i+7] = sum over slabs k = 0..S-1 (in order, fp32) of bf16 slab elements (one 16-B load
 // per slab), (+ beta out): the deferred tail and the standalone reduce of bf16 slabs (same bits)
@@ -248,7 +300,8 @@ extern int g_gemm_max_grid;
 extern int g_gemm_group_p8;
 extern int g_gemm_group_pk;
 extern int g_gemm_n96;
-extern int g_red_side;
+// cg_set_tuning("linear_rows_nb", n): cg_linear_rows_f32's kernel above 2048 rows (rows_f32.hip)
+extern int g_linear_rows_nb;
 // test knob (cg_set_tuning("pk_flags", f)) for the persistent kernel's epilogue (gemm_pk.hip)
 extern int g_pk_flags;
 int gemm_cu_count();  // compute units of the current device (cached; gemm_pk.hip)

@@ -4,6 +4,11 @@
 #pragma once
 #include "common.h"
 
+namespace cg {
+// cg_set_tuning knobs of the LayerNorm backward (layernorm.hip)
+extern int g_ln_rpb, g_ln_waves, g_ln_pf, g_ln_rl, g_ln_nt;
+}  // namespace cg
+
 namespace {
 using namespace cg;
 

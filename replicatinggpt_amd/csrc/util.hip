@@ -1,8 +1,11 @@
-// charpt: error plumbing, counters, RNG helpers, reductions, batch gather.
+// charpt: error plumbing, counters, RNG helpers, sums, batch gather, timing events, and the tuning
+// knobs' one setter (cg_set_tuning).
+#include <limits.h>
 #include <stdarg.h>
 
-#include "common.h"
+#include "attention_common.h"
 #include "defer.h"
+#include "ln_fwd.h"
 
 namespace cg {
 static thread_local char g_err[1024] = "";
@@ -113,170 +116,6 @@ extern "C" int cg_dropout_apply(const float* x, int64_t rows, int64_t C, int64_t
     return CG_OK;
 }
 
-// --------------------------------------------------------------------------------------
-// column reduction of per-block partials [K][N] (LayerNorm dgamma/dbeta, bias column sums):
-// 16 columns x 64 row-lanes per block, float4 loads, all of a lane's rows (8 at K = 512) in flight,
-// then the 64 row-lane sums added in a fixed order (deterministic).  The former 32-column blocks
-// (72 blocks at C4, 8 loads in flight per lane) ran 130 us for 9.4 MB.
-// Column n goes to out_a[n] (n < S), out_b[n - S] (n < 2S) or out_c[n - 2S]; NULL drops it.
-// One block's work (block blk of the job's ceil(N / 16)): shared by the single-job kernel and the
-// deferred multi-job one, so both give the same bits.
-__device__ __forceinline__ void reduce_partials_block(const float* __restrict__ part, int64_t K, int64_t N,
-                                                      float* __restrict__ out_a, float* __restrict__ out_b,
-                                                      float* __restrict__ out_c, int64_t S, int accumulate,
-                                                      int accumulate_c, int64_t blk, float (*red)[17]) {
-    const int cq = threadIdx.x & 3, rl = threadIdx.x >> 2;
-    const int64_t n0 = blk * 16 + 4 * cq;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if ((N & 3) == 0 && (((uintptr_t)part) & 15) == 0) {
-        if (n0 < N) {
-            int64_t k = rl;
-            for (; k + 7 * 64 < K; k += 8 * 64) {
-                float4 v[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = *(const float4*)(part + (k + 64 * j) * N + n0);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    a[0] += v[j].x;
-                    a[1] += v[j].y;
-                    a[2] += v[j].z;
-                    a[3] += v[j].w;
-                }
-            }
-            for (; k < K; k += 64) {
-                const float4 v = *(const float4*)(part + k * N + n0);
-                a[0] += v.x;
-                a[1] += v.y;
-                a[2] += v.z;
-                a[3] += v.w;
-            }
-        }
-    } else {
-        for (int64_t k = rl; k < K; k += 64)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (n0 + q < N) a[q] += part[k * N + n0 + q];
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) red[rl][4 * cq + q] = a[q];
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        const int c = threadIdx.x;
-        const int64_t n = blk * 16 + c;
-        if (n < N) {
-            float t = 0.f;
-            for (int j = 0; j < 64; ++j) t += red[j][c];
-            float* dst;
-            int acc = accumulate;
-            if (n < S) dst = out_a ? out_a + n : nullptr;
-            else if (n < 2 * S) dst = out_b ? out_b + (n - S) : nullptr;
-            else {
-                dst = out_c ? out_c + (n - 2 * S) : nullptr;
-                acc = accumulate_c;
-            }
-            if (dst) *dst = acc ? *dst + t : t;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_reduce_partials(const float* __restrict__ part, int64_t K, int64_t N,
-                                                         float* __restrict__ out_a, float* __restrict__ out_b,
-                                                         float* __restrict__ out_c, int64_t S, int accumulate,
-                                                         int accumulate_c) {
-    __shared__ float red[64][17];
-    reduce_partials_block(part, K, N, out_a, out_b, out_c, S, accumulate, accumulate_c, blockIdx.x, red);
-}
-
-__global__ __launch_bounds__(256) void k_reduce_partials_multi(cg::PartJobs jobs) {
-    __shared__ float red[64][17];
-    const int b = blockIdx.x;
-    int q = 0;
-    while (q + 1 < jobs.n && b >= jobs.start[q + 1]) ++q;
-    const cg::PartJob& j = jobs.j[q];
-    reduce_partials_block(j.part, j.K, j.N, j.a, j.b, j.c, j.S, j.acc, j.acc_c, b - jobs.start[q], red);
-}
-
-namespace cg {
-// Deferred column-sum reduces (the CG_DEFER calls: cg_layernorm_bwd_reduce_ex, cg_reduce_rows_ex,
-// cg_head_bwd_ex; the caller keeps every queued job's partials allocated and reads no output before
-// cg_flush_deferred on that stream).  The training backward queues its ~20 LayerNorm / bias-gradient
-// reduces and the flush launches them as ONE kernel: on one hardware queue each was a ~5 us launch
-// for ~1 us of work.  The queue is the stream's DeferQueue (defer.h).
-void flush_parts_locked(DeferQueue& q) {
-    if (!q.parts.n) return;
-    const PartJobs jobs = q.parts;
-    q.parts.n = 0;
-    k_reduce_partials_multi<<<jobs.start[jobs.n], 256, 0, q.stream>>>(jobs);
-}
-
-// [p, p + n) of job j's outputs
-static bool overlaps(const float* p, int64_t n, const float* q, int64_t m) {
-    return p && q && n > 0 && m > 0 && p < q + m && q < p + n;
-}
-static bool job_outputs_overlap(const PartJob& x, const float* p, int64_t n) {
-    return overlaps(x.a, x.S, p, n) || overlaps(x.b, x.S, p, n) || overlaps(x.c, x.N - 2 * x.S, p, n);
-}
-// an immediate reduce / write into [p, p + n) on stream st: that stream's queued jobs that target it
-// go first (caller holds the registry lock)
-void flush_parts_touching_locked(DeferQueue* q, const float* p, int64_t n) {
-    if (!q) return;
-    for (int i = 0; i < q->parts.n; ++i)
-        if (job_outputs_overlap(q->parts.j[i], p, n)) {
-            flush_parts_locked(*q);
-            return;
-        }
-}
-
-static void enqueue_partials(const PartJob& j, hipStream_t st) {
-    std::lock_guard<std::mutex> lk(defer_mutex());
-    DeferQueue& q = *defer_queue(st, true);
-    PartJobs& P = q.parts;
-    bool clash = P.n == MAX_PART_JOBS;
-    for (int i = 0; i < P.n && !clash; ++i) {
-        const PartJob& x = P.j[i];
-        clash = job_outputs_overlap(x, j.a, j.S) || job_outputs_overlap(x, j.b, j.S) ||
-                job_outputs_overlap(x, j.c, j.N - 2 * j.S);
-    }
-    if (clash) flush_parts_locked(q);
-    if (!P.n) P.start[0] = 0;
-    P.j[P.n] = j;
-    P.start[P.n + 1] = P.start[P.n] + (int)ceil_div(j.N, 16);
-    ++P.n;
-}
-
-void launch_reduce_partials(const float* part, int64_t K, int64_t N, float* out_a, float* out_b, int64_t S,
-                            int accumulate, hipStream_t st) {
-    {
-        std::lock_guard<std::mutex> lk(defer_mutex());
-        DeferQueue* q = defer_queue(st, false);
-        flush_parts_touching_locked(q, out_a, S);
-        flush_parts_touching_locked(q, out_b, N - S);
-    }
-    k_reduce_partials<<<ceil_div(N, 16), 256, 0, st>>>(part, K, N, out_a, out_b, nullptr, S, accumulate, 0);
-}
-void launch_reduce_partials3(const float* part, int64_t K, int64_t N, float* out_a, float* out_b, float* out_c,
-                             int64_t S, int accumulate, int accumulate_c, hipStream_t st) {
-    {
-        std::lock_guard<std::mutex> lk(defer_mutex());
-        DeferQueue* q = defer_queue(st, false);
-        flush_parts_touching_locked(q, out_a, S);
-        flush_parts_touching_locked(q, out_b, S);
-        flush_parts_touching_locked(q, out_c, N - 2 * S);
-    }
-    k_reduce_partials<<<ceil_div(N, 16), 256, 0, st>>>(part, K, N, out_a, out_b, out_c, S, accumulate, accumulate_c);
-}
-// the deferrable forms (cg_layernorm_bwd_reduce_ex, cg_reduce_rows_ex, cg_head_bwd_ex): queued on the
-// stream's DeferQueue with CG_DEFER, else launched now
-void reduce_partials_deferrable(const float* part, int64_t K, int64_t N, float* out_a, float* out_b, float* out_c,
-                                int64_t S, int accumulate, int accumulate_c, int defer, hipStream_t st) {
-    if (defer) {
-        enqueue_partials(PartJob{part, K, N, S, out_a, out_b, out_c, accumulate, accumulate_c}, st);
-        return;
-    }
-    launch_reduce_partials3(part, K, N, out_a, out_b, out_c, S, accumulate, accumulate_c, st);
-}
-}  // namespace cg
-
 // deterministic two-pass sum: pass 1 -> one partial per block (fixed order), pass 2 one block
 __global__ void k_sum_partial(const float* x, int64_t n, float* part) {
     __shared__ float red[16];
@@ -359,4 +198,128 @@ extern "C" int cg_gather_batch(const void* data, int data_is_u8, const int64_t* 
         k_gather_batch<int64_t><<<grid, 256, 0, (hipStream_t)stream>>>((const int64_t*)data, ix, x, y, B, T);
     CG_LAUNCH_CHECK("cg_gather_batch");
     return CG_OK;
+}
+
+extern "C" int cg_timing_event_create(void** event) {
+    CG_REQUIRE(event, "cg_timing_event_create: null");
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess) {
+        cg::set_error("cg_timing_event_create: hipEventCreate failed");
+        return CG_EHIP;
+    }
+    *event = (void*)e;
+    return CG_OK;
+}
+
+extern "C" int cg_timing_event_record(void* event, void* stream) {
+    CG_REQUIRE(event, "cg_timing_event_record: null event");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    unsigned long long id = 0;
+    hipGraph_t g = nullptr;
+    const hipGraphNode_t* deps = nullptr;
+    size_t nd = 0;
+    hipError_t r = hipStreamGetCaptureInfo_v2(st, &cs, &id, &g, &deps, &nd);
+    if (r == hipSuccess && cs == hipStreamCaptureStatusActive) {
+        // an event-record node appended to the capture by hand (hipEventRecordWithFlags with
+        // hipEventRecordExternal is refused during capture on this runtime): it depends on the
+        // stream's current capture frontier and becomes the new frontier
+        hipGraphNode_t node = nullptr;
+        r = hipGraphAddEventRecordNode(&node, g, deps, nd, (hipEvent_t)event);
+        if (r == hipSuccess) r = hipStreamUpdateCaptureDependencies(st, &node, 1, hipStreamSetCaptureDependencies);
+    } else if (r == hipSuccess) {
+        r = hipEventRecord((hipEvent_t)event, st);
+    }
+    if (r != hipSuccess) {
+        (void)hipGetLastError();   // leave no sticky error for the caller's next launch check
+        cg::set_error("cg_timing_event_record: %s", hipGetErrorString(r));
+        return CG_EHIP;
+    }
+    return CG_OK;
+}
+
+extern "C" int cg_timing_event_elapsed(void* start, void* end, float* ms) {
+    CG_REQUIRE(start && end && ms, "cg_timing_event_elapsed: null");
+    const hipError_t r = hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)end);
+    if (r != hipSuccess) {
+        cg::set_error("cg_timing_event_elapsed: %s", hipGetErrorString(r));
+        return CG_EHIP;
+    }
+    return CG_OK;
+}
+
+extern "C" int cg_timing_event_destroy(void* event) {
+    if (event) (void)hipEventDestroy((hipEvent_t)event);
+    return CG_OK;
+}
+
+namespace {
+#ifdef CG_AB_VARIANTS
+constexpr bool AB_BUILD = true;
+#else
+constexpr bool AB_BUILD = false;   // the measured-slower A/B variants exist only in libcharpt_hip_ab.so (`make ab`)
+#endif
+constexpr int ANY_LO = INT_MIN, ANY_HI = INT_MAX;
+constexpr int AB_LO(int lo) { return AB_BUILD ? ANY_LO : lo; }   // a bound only the product build applies
+constexpr int AB_HI(int hi) { return AB_BUILD ? ANY_HI : hi; }
+
+struct Knob {
+    const char* key;
+    int* knob;
+    int lo, hi;   // accepted values, inclusive
+};
+const Knob KNOBS[] = {
+    // gemm.hip: kernel choice; 0 automatic -- the product build takes only gemm_variant_in_product's values
+    {"gemm_variant", &g_gemm_variant, ANY_LO, ANY_HI},
+    {"gemm_max_grid", &g_gemm_max_grid, ANY_LO, ANY_HI},   // gemm.hip: cap on persistent-kernel blocks, 0 = resident slots
+    {"gemm_group_p8", &g_gemm_group_p8, 0, 255},   // gemm.hip: gemm_tile.h tile_rc row panels per group (0/1: row-major)
+    {"gemm_group_pk", &g_gemm_group_pk, 0, 255},   // gemm.hip: the same for k_gemm_pk
+    {"gemm_n96", &g_gemm_n96, ANY_LO, ANY_HI},     // gemm.hip: 128x96 tiles for the part-filling fp32 residual forwards
+    {"pk_flags", &g_pk_flags, ANY_LO, ANY_HI},     // gemm_pk.hip: the persistent kernels' epilogue / what-if bits
+    {"linear_rows_nb", &g_linear_rows_nb, 0, 2},   // rows_f32.hip: 0 k_linear_f32q (16-row waves), 1 / 2 k_linear_f32t
+    {"skip_splitk_reduce", &g_skip_splitk_reduce, ANY_LO, ANY_HI},   // defer.hip: WRONG results, timing only
+    {"adam_per_launch", &g_adam_per_launch, ANY_LO, ANY_HI},   // defer.hip: AdamW jobs per launch's free blocks
+    {"adam_batch", &g_adam_batch, AB_LO(1), AB_HI(1)},   // defer.hip: side-block AdamW chunks in flight (A/B: 4, 5)
+    {"red_side", &g_red_side, ANY_LO, ANY_HI},     // defer.hip: part-filling launches take a pending reduce on extra blocks
+    // attention_d64.hip: 0 automatic, 1 ring kernels at T <= 256 (and the 64-query-block fp32 forward instead of
+    // the sequence-resident one), 2 separate resident dQ / dK-dV launches (A/B build also 4: the 8-wave
+    // ping-pong forward at T % 256 == 0, 512..1024)
+    {"attn_variant", &g_attn_variant, AB_LO(0), AB_HI(2)},
+    {"attn_bwd_lpt", &g_attn_bwd_lpt, 0, 1},       // attention_d64.hip: merged resident backward order (1 = dK/dV first)
+    {"decode_attn_rows", &g_decode_attn_rows, 0, 1},   // decode.hip: the coalesced-chunk phase-1 decode attention
+    {"adamw_mode", &g_adamw_mode, 0, 5},           // ce_adamw.hip: cg_adamw's kernel form, 0 = by size
+    {"ln_rl", &g_ln_rl, 0, 2},   // layernorm.hip: backward rows' next loads before the current stores (2: also at C = 768)
+    {"ln_nt", &g_ln_nt, ANY_LO, ANY_HI},           // layernorm.hip: the backward's non-temporal streams (-1 automatic, 0..3)
+    {"ln_pf", &g_ln_pf, ANY_LO, ANY_HI},           // layernorm.hip: next row's loads before the current row
+    {"ln_waves", &g_ln_waves, ANY_LO, ANY_HI},     // layernorm.hip: takes effect for workspaces sized after the call
+    {"ln_rpb", &g_ln_rpb, ANY_LO, ANY_HI},         // layernorm.hip: takes effect for workspaces sized after the call
+};
+
+// product build: automatic (0), the register-staged fallback (2), the persistent 128x128 (9) and 256x256 (24)
+// tiles, k_gemm_f32 for every fp32 product (98: not the small-M or persistent kernels; 97: k_gemm_f32s, not the
+// K-resident one; 96: the persistent k_gemm_f32p at any M), the generic kernels (99); the measured-slower A/B
+// tiles (among them 26, the 256x256 tile on the staggered 8-phase schedule) only in the A/B build
+bool gemm_variant_in_product(int v) {
+    return v == 0 || v == 2 || v == 9 || v == 24 || v == 96 || v == 97 || v == 98 || v == 99;
+}
+}  // namespace
+
+extern "C" int cg_set_tuning(const char* key, int value) {
+    CG_REQUIRE(key, "cg_set_tuning: null key");
+    if (!strcmp(key, "defer_splitk") || !strcmp(key, "slab_bf16") || !strcmp(key, "defer_partials")) {
+        set_error("cg_set_tuning: %s is a per-call flag since round 5 (cg_epilogue_t.flags CG_GEMM_DEFER_REDUCE / "
+                  "CG_GEMM_SLAB_BF16, the CG_DEFER flag of the _ex reduces)", key);
+        return CG_EINVAL;
+    }
+    for (const Knob& k : KNOBS) {
+        if (strcmp(key, k.key)) continue;
+        const bool ok = value >= k.lo && value <= k.hi &&
+                        (AB_BUILD || k.knob != &g_gemm_variant || gemm_variant_in_product(value));
+        CG_REQUIRE(ok, "cg_set_tuning: %s = %d is not accepted by this build (out of range, or an A/B variant: make ab)",
+                   key, value);
+        *k.knob = value;
+        return CG_OK;
+    }
+    set_error("cg_set_tuning: unknown key %s", key);
+    return CG_EINVAL;
 }

@@ -499,7 +499,7 @@ def adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, p_bf16: Optional[Tensor], 
 def adamw_defer(p: Tensor, g: Tensor, m: Tensor, v: Tensor, p_bf16: Tensor, lr: float, beta1: float, beta2: float,
                 eps: float, weight_decay: float, step: Tensor) -> None:
     """adamw over one region, queued: run by the free blocks of the next part-filling persistent GEMM
-    launch on this stream, or by cg_flush_deferred (csrc gemm.hip cg_adamw_defer); same bits."""
+    launch on this stream, or by cg_flush_deferred (csrc defer.hip cg_adamw_defer); same bits."""
     L.check(L.load().cg_adamw_defer(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(p_bf16), p.numel(), lr, beta1,
                                     beta2, eps, weight_decay, L.ptr(step), _s(p)), "adamw_defer")
 

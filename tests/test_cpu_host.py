@@ -186,3 +186,62 @@ def test_gemm_operand_extent_guard():
     with pytest.raises(ValueError, match="operand C"):
         _gemm_extents(torch.empty(256, 64), torch.empty(32, 64), torch.empty(255, 32), False, False, 256, 32, 64, 64,
                       64, 32)
+
+
+_SET_TUNING_CHILD = r"""
+import json, sys
+from replicatinggpt_amd import _lib
+lib = _lib.load()
+OK, EINVAL = 0, 1
+bad = []
+
+def want(key, value, rc, names_key=False):
+    got = lib.cg_set_tuning(None if key is None else key.encode(), value)
+    if got != rc:
+        bad.append((key, value, got, rc))
+    elif names_key and key not in lib.cg_last_error_string().decode():
+        bad.append((key, value, "error text lacks the key", lib.cg_last_error_string().decode()))
+
+table = {
+    "gemm_variant": ([0, 2, 9, 24, 96, 97, 98, 99], [1, 26]),
+    "linear_rows_nb": ([0, 1, 2], [-1, 3]),
+    "gemm_group_p8": ([0, 255], [-1, 256]),
+    "gemm_group_pk": ([0, 255], [-1, 256]),
+    "ln_rl": ([0, 1, 2], [3]),
+    "decode_attn_rows": ([0, 1], [2]),
+    "attn_bwd_lpt": ([0, 1], [2]),
+    "attn_variant": ([0, 1, 2], [3, 4]),
+    "adam_batch": ([1], [2]),
+    "adamw_mode": ([0, 5], [-1, 6]),
+}
+for key, (ok, refused) in table.items():
+    for v in ok:
+        want(key, v, OK)
+    for v in refused:
+        want(key, v, EINVAL)
+for key in ["gemm_max_grid", "gemm_n96", "pk_flags", "skip_splitk_reduce", "adam_per_launch", "red_side", "ln_waves",
+            "ln_nt", "ln_pf", "ln_rpb"]:
+    for v in (-7, 0, 12345):
+        want(key, v, OK)
+for key in ["defer_splitk", "slab_bf16", "defer_partials", "no_such_knob"]:
+    for v in (0, 1):
+        want(key, v, EINVAL, names_key=True)
+want(None, 0, EINVAL)
+print(json.dumps(bad))
+"""
+
+
+def test_set_tuning_contract():
+    """cg_set_tuning's accept / refuse contract in the product library: each key's accepted range, the
+    retired per-call keys, unknown and null keys.  A fresh interpreter, so no knob leaks into other tests."""
+    import os
+    import subprocess
+    import sys
+    if os.environ.get("CHARPT_LIB"):
+        pytest.skip("CHARPT_LIB names another build; the contract is the product library's")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("CHARPT_TUNING", "CHARPT_WHATIF")}
+    r = subprocess.run([sys.executable, "-c", _SET_TUNING_CHILD], capture_output=True, text=True, timeout=240, env=env,
+                       cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1]) == []

@@ -1,6 +1,6 @@
 """The decode engine (replicatinggpt_amd/decode.py, csrc/decode.hip, the fp32 row kernels of
-csrc/gemm.hip) on the MI355X against the fp64 CPU oracle, through every dispatch branch and A/B
-switch, plus the device sampler against an exact expectation and the row kernels with the strides
+csrc/rows_f32.hip and csrc/gemm_f32.hip) on the MI355X against the fp64 CPU oracle, through every
+dispatch branch and A/B switch, plus the device sampler against an exact expectation and the row kernels with the strides
 and views the engine hands them.
 
 Teacher forcing: the oracle is given the engine's own output as context, so one near-tie decides one

@@ -1,5 +1,5 @@
 """Where does the persistent fp32 GEMM (k_gemm_f32p, generate()'s window products) spend its time?
-Loads the what-if build (make -C replicatinggpt_amd/csrc whatif; gemm.hip CG_F32P_WHATIF) and times the
+Loads the what-if build (make -C replicatinggpt_amd/csrc whatif; gemm_f32.hip CG_F32P_WHATIF) and times the
 four C5 window shapes with pk_flags 0 (all), 16 (no in-loop loads), 32 (no MFMAs), 64 (no epilogue
 stores), 256 (fragment reads only in a tile's first K-step), 512 (LDS store + barrier only
 there) and combinations.  Wrong results (timing only).  GPU only.
