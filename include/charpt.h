@@ -368,6 +368,26 @@ int cg_decode_attn(const float* q, int64_t ldq, const float* k, const float* v, 
    with u from Philox(*seed_dev, stream = len, counter = b)                                        */
 int cg_decode_sample(const float* logits, int64_t ldl, int64_t V, int64_t B, int greedy, const uint64_t* seed_dev,
                      const int64_t* len_dev, int64_t* idx, int64_t ld, void* stream);
+/* cg_decode_sample's draw with a temperature, a top-k cut and a nucleus (top-p) cut, in HF's order
+   (temperature, top-k, top-p on the renormalised top-k distribution).  params_dev: three device
+   floats {tau, k, p} read when the kernel runs (a captured graph serves every setting): tau > 0;
+   k = 0 or k >= V: top-k off; 0 < p <= 1, p = 1: top-p off.  Per row of fp32 logits x[0..V):
+     1. rank by logit descending, the lower index first among equals (compared on the raw logits);
+     2. w[v] = exp((x[v] - max x) / tau); a -inf logit has weight 0;
+     3. keep the first min(k, V) ranked tokens (all when top-k is off); S_k = the sum of their weights;
+     4. p < 1: of those keep the shortest rank-order prefix whose weight reaches p * S_k (never
+        fewer than one token);
+     5. u24 = Philox4x32-10(counter (row, 0, len, 0), key *seed_dev)[0] >> 8, t = u24 / 2^24 * S with
+        S the kept weights' sum; the token is the first kept v in vocabulary order with t < the kept
+        weight summed through v, else the last kept v.  idx[row, len] <- token (len = *len_dev);
+        nothing else is written.
+   tau = 1 with both cuts off: bit for bit the token cg_decode_sample(greedy = 0) writes.  k = 1, or
+   a p so small that the top token alone reaches p * S_k: the greedy token.  A row holding NaN or
+   +inf: the greedy rule's token (the first NaN's index, else the first +inf's).  The token is always
+   inside [0, V).  1 <= V <= 1024 and ldl >= V, else CG_EINVAL.                                    */
+int cg_decode_sample_filtered(const float* logits, int64_t ldl, int64_t V, int64_t B, const float* params_dev,
+                              const uint64_t* seed_dev, const int64_t* len_dev, int64_t* idx, int64_t ld,
+                              void* stream);
 
 /* ---- fused AdamW over a flat fp32 buffer (torch.optim.AdamW, GPT1.py:218,233) ------------
    step_ptr: device int64 step count (already incremented for this step).

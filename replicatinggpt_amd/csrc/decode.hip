@@ -8,8 +8,9 @@
 //   phase 2 (sliding window): the full window forward (cg_decode_window gathers it), last row only
 //            through ln_f / lm_head;
 // and samples on the device (cg_decode_sample: argmax, or inverse-CDF sampling from a Philox
-// stream).  Every step's shapes are static and the current length lives in device memory, so each
-// phase is captured once as a hipGraph and replayed per token.
+// stream; cg_decode_sample_filtered: that draw under a temperature, a top-k and a top-p cut read
+// from device memory).  Every step's shapes are static and the current length lives in device
+// memory, so each phase is captured once as a hipGraph and replayed per token.
 #include "common.h"
 
 namespace cg {
@@ -316,6 +317,172 @@ __global__ __launch_bounds__(64) void k_decode_sample(const float* __restrict__ 
     if (lane == 0) idx[b * ld + len] = tok;
 }
 
+// k_decode_sample's draw with a temperature, a top-k cut and a nucleus (top-p) cut, all three read from
+// device memory (params = {tau, k, p}: one captured graph serves every setting); the contract is
+// include/charpt.h's.  One 256-thread block per row, V <= SAMPLE_VMAX, the row in LDS:
+//   xs  the logits (padded to a float4 with -inf: a pad entry is ahead of nothing in the ranking);
+//   wv  the weights exp((x - max) / tau) in vocabulary order, then the kept ones (dropped: +0);
+//   ws  the weights in rank order (ws[rank[v]] = wv[v]).
+// Thread t owns columns t + 256 j: its ranks stay in registers.  The rank of v is the number of
+// columns ahead of it (greater, or equal with a lower index: argmax_ahead's order on rows without
+// NaN), counted against the whole row read as broadcast float4s -- V^2 / 256 compares per thread,
+// 17 float4 reads at V = 65; skipped when both cuts are off.  Wave 0 then sums the first k' ranked
+// weights, finds the nucleus prefix with a 64-wide inclusive scan per chunk, and draws exactly as
+// k_decode_sample does over wv: the lane-strided sum + wave_sum for S, lane 0's sequential scan in
+// vocabulary order.  A dropped column adds +0 there, which changes no partial sum and so can never
+// be the first column past the draw: with everything kept and tau = 1 (x / 1.0f is exact) the token
+// is k_decode_sample's bit for bit.
+constexpr int SAMPLE_VMAX = 1024;
+__global__ __launch_bounds__(256) void k_decode_sample_filtered(const float* __restrict__ logits, int64_t ldl,
+                                                                int V, int64_t B,
+                                                                const float* __restrict__ params,
+                                                                const uint64_t* __restrict__ seed_dev,
+                                                                const int64_t* __restrict__ len_dev,
+                                                                int64_t* __restrict__ idx, int64_t ld) {
+    constexpr int NT = 256, J = SAMPLE_VMAX / NT;
+    __shared__ float4 xs4[SAMPLE_VMAX / 4], wv4[SAMPLE_VMAX / 4];
+    __shared__ float ws[SAMPLE_VMAX];
+    __shared__ int sh_keep, sh_last;
+    float* xs = (float*)xs4;
+    float* wv = (float*)wv4;
+    const int64_t b = blockIdx.x;
+    if (b >= B) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const float* row = logits + b * ldl;
+    const int Vp = (V + 3) & ~3;
+    const int nj = (V + NT - 1) / NT;   // column passes in use (1 up to V = 256)
+    // every scalar the kernel needs, loaded beside the row (not one global round trip after another)
+    const float tau = params[0], kf = params[1], p = params[2];
+    const int64_t len = *len_dev;
+    const uint64_t seed = seed_dev ? *seed_dev : 0ull;
+    for (int v = tid; v < Vp; v += NT) xs[v] = v < V ? row[v] : -INFINITY;
+    if (tid == 0) sh_last = -1;
+    __syncthreads();
+    // the greedy token (k_decode_sample's loop), in every wave: block-uniform without a broadcast
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int v = lane; v < V; v += 64) {
+        const float x = xs[v];
+        if (argmax_ahead(x, v, best, bi)) { best = x; bi = v; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        if (argmax_ahead(ob, oi, best, bi)) { best = ob; bi = oi; }
+    }
+    if (best != best || best == INFINITY) {   // a NaN or +inf in the row: the greedy rule's token
+        if (tid == 0) idx[b * ld + len] = bi;
+        return;
+    }
+    const int kk = kf >= 1.f && kf < (float)V ? (int)kf : V;   // 0, k >= V (and NaN): top-k off
+    const bool nucleus = p < 1.f;                                // p >= 1 (and NaN): top-p off
+    const bool filtered = kk < V || nucleus;
+    float w[J];
+    int rank[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int v = tid + NT * j;
+        w[j] = 0.f;
+        rank[j] = 0;
+        if (j < nj) {   // block-uniform
+            const float x = v < V ? xs[v] : -INFINITY;
+            w[j] = x == -INFINITY ? 0.f : __expf((x - best) / tau);
+            if (v < Vp) wv[v] = w[j];
+        }
+    }
+    int keep = V;
+    if (filtered) {   // block-uniform
+        if (tid < V) {   // a thread with no column skips the pass (its J columns are all past V)
+            float xv[J];
+#pragma unroll
+            for (int j = 0; j < J; ++j) xv[j] = tid + NT * j < V ? xs[tid + NT * j] : INFINITY;
+            for (int u = 0; u < Vp; u += 4) {
+                const float4 q = xs4[u >> 2];
+                const float xu[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int j = 0; j < J; ++j) {
+                    if (j < nj) {   // block-uniform
+                        const int v = tid + NT * j;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)   // no short circuit: compares and bit operations, no branches
+                            rank[j] += (int)((xu[e] > xv[j]) | ((xu[e] == xv[j]) & (u + e < v)));
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < J; ++j)
+                if (tid + NT * j < V) ws[rank[j]] = w[j];   // ranks are a permutation of 0..V-1
+        }
+        __syncthreads();
+        if (tid < 64) {
+            float sk = 0.f;
+            for (int r = lane; r < kk; r += 64) sk += ws[r];
+            sk = wave_sum(sk);
+            int n = kk;
+            if (nucleus) {
+                // the shortest rank-order prefix whose weight reaches p * S_k (at least one token)
+                const float thr = p * sk;
+                float carry = 0.f;
+                for (int base = 0; base < kk; base += 64) {
+                    const int r = base + lane;
+                    float c = r < kk ? ws[r] : 0.f;
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const float t = __shfl_up(c, o, 64);
+                        if (lane >= o) c += t;
+                    }
+                    c += carry;
+                    const unsigned long long hit = __ballot(r < kk && c >= thr);
+                    if (hit) {   // wave-uniform
+                        n = base + __ffsll(hit);
+                        break;
+                    }
+                    carry = __shfl(c, 63, 64);
+                }
+            }
+            if (lane == 0) sh_keep = n;
+        }
+        __syncthreads();
+        keep = sh_keep;
+        int last = -1;
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            const int v = tid + NT * j;
+            if (v < V) {
+                if (rank[j] < keep) last = v;   // v grows with j
+                else wv[v] = 0.f;
+            }
+        }
+        if (last >= 0) atomicMax(&sh_last, last);
+    }
+    __syncthreads();
+    if (tid >= 64) return;
+    // the draw: k_decode_sample's sum pattern and sequential scan over the kept weights
+    float s = 0.f;
+    for (int v = lane; v < V; v += 64) s += wv[v];
+    s = wave_sum(s);
+    const u32x4 r = philox_group(seed, (uint64_t)len, (uint64_t)b);
+    const float u = (float)(r.x >> 8) * (1.0f / 16777216.0f) * s;  // 24-bit uniform in [0, s)
+    if (lane == 0) {
+        int tok = filtered ? sh_last : V - 1;   // no column past the draw: the last kept one
+        float c = 0.f;
+        bool found = false;
+        float4 next = wv4[0];
+        for (int v = 0; v < Vp && !found; v += 4) {   // a float4 of weights per LDS read; pad weights are 0
+            const float4 q = next;
+            if (v + 4 < Vp) next = wv4[(v >> 2) + 1];   // in flight under this float4's additions
+            const float wq[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                c += wq[e];
+                if (!found && u < c) { tok = v + e; found = true; }
+            }
+        }
+        idx[b * ld + len] = tok;
+    }
+}
+
 }  // namespace
 
 extern "C" int cg_decode_window(const int64_t* idx, int64_t ld, int64_t B, int64_t T, const int64_t* len_dev,
@@ -375,5 +542,18 @@ extern "C" int cg_decode_sample(const float* logits, int64_t ldl, int64_t V, int
     k_decode_sample<<<(unsigned)B, 64, 0, (hipStream_t)stream>>>(logits, ldl, V, B, greedy, seed_dev, len_dev, idx,
                                                                  ld);
     CG_LAUNCH_CHECK("cg_decode_sample");
+    return CG_OK;
+}
+
+extern "C" int cg_decode_sample_filtered(const float* logits, int64_t ldl, int64_t V, int64_t B,
+                                         const float* params_dev, const uint64_t* seed_dev, const int64_t* len_dev,
+                                         int64_t* idx, int64_t ld, void* stream) {
+    CG_REQUIRE(B > 0 && V > 0 && ldl >= V, "cg_decode_sample_filtered: bad sizes");
+    CG_REQUIRE(V <= SAMPLE_VMAX, "cg_decode_sample_filtered: V = %lld is above the kernel's limit of %d",
+               (long long)V, SAMPLE_VMAX);
+    CG_REQUIRE(logits && params_dev && len_dev && idx, "cg_decode_sample_filtered: null pointer");
+    k_decode_sample_filtered<<<(unsigned)B, 256, 0, (hipStream_t)stream>>>(logits, ldl, (int)V, B, params_dev,
+                                                                           seed_dev, len_dev, idx, ld);
+    CG_LAUNCH_CHECK("cg_decode_sample_filtered");
     return CG_OK;
 }

@@ -16,7 +16,13 @@ computed as:
 * sampling on the device (``cg_decode_sample``): greedy = argmax (torch.argmax tie rule, the
   parity mode), else inverse-CDF draws from a Philox stream keyed by (seed, length, row) --
   torch.multinomial's CPU-generator stream is not reproducible on a GPU, so the sampled
-  (non-greedy) stream is charpt's own, statistically the same distribution.
+  (non-greedy) stream is charpt's own, statistically the same distribution;
+* a filtered engine (``filtered=True``: generate()'s temperature / top_k / top_p) samples with
+  ``cg_decode_sample_filtered`` instead -- the same Philox draw over the tokens the top-k and
+  nucleus cuts keep, weights at the temperature.  The three settings live in a device buffer the
+  kernel reads when it runs, so ``generate(..., sampling=(t, k, p))`` rewrites twelve bytes and
+  replays the graphs captured once; neutral settings there give ``cg_decode_sample``'s tokens
+  bit for bit.
 
 The current length lives in a device int64, so each phase's step is one static-shape hipGraph
 captured once and replayed per token (prefill of a longer prompt replays the phase-1 graph without
@@ -28,6 +34,7 @@ import torch
 
 from . import functional as Fn
 from . import ops
+from .sampling import check_sampling, sampling_params
 
 # CHARPT_DECODE_ROWS=0: the per-token LayerNorms in their own launches before ln1/ln2/lnf's Linears (A/B)
 DECODE_ROWS = os.environ.get("CHARPT_DECODE_ROWS", "1") == "1"
@@ -36,8 +43,10 @@ LAST_KV_SPLIT = os.environ.get("CHARPT_LAST_KV_SPLIT", "1") == "1"
 
 
 class DecodeEngine:
-    def __init__(self, model, batch, max_len, greedy=True, seed=0, use_graph=True):
+    def __init__(self, model, batch, max_len, greedy=True, seed=0, use_graph=True, filtered=False):
         cfg = model.config
+        if filtered and greedy:
+            raise ValueError("DecodeEngine: filtered sampling and greedy exclude each other")
         self.m, self.B, self.max_len = model, int(batch), int(max_len)
         self.T, self.C, self.H = cfg.block_size, cfg.n_embd, cfg.n_head
         self.D = self.C // self.H
@@ -51,6 +60,9 @@ class DecodeEngine:
         self.idx = torch.zeros((B, self.max_len), dtype=torch.int64, device=dev)
         self.len = torch.zeros(1, dtype=torch.int64, device=dev)
         self.seed = torch.full((1,), int(seed), dtype=torch.int64, device=dev)   # read by the sampler
+        self.filtered = bool(filtered)
+        # (temperature, top_k, top_p), read by the filtered sampler when it runs
+        self.params = sampling_params().to(dev) if self.filtered else None
         self.kc = torch.zeros((self.L, B, self.H, self.T, self.D), dtype=torch.float32, device=dev)
         self.vc = torch.zeros_like(self.kc)
         self.win = torch.empty((B, self.T), dtype=torch.int64, device=dev)
@@ -102,6 +114,12 @@ class DecodeEngine:
     def _head(self, x2):
         self._ln_linear(x2, "lnf", self._R("lm_w").operand(self.act), self.logits, bias=self._b("lm_b"))
 
+    def _sample(self):
+        if self.filtered:
+            ops.decode_sample_filtered(self.logits, self.params, self.seed, self.len, self.idx)
+        else:
+            ops.decode_sample(self.logits, self.greedy, self.seed, self.len, self.idx)
+
     # -- phase 1: one token against the K/V caches ---------------------------------------------
     def _step1(self, sample):
         C, B = self.C, self.B
@@ -131,7 +149,7 @@ class DecodeEngine:
             x = self._ffn_tail(l, x2)
         if sample:
             self._head(x)
-            ops.decode_sample(self.logits, self.greedy, self.seed, self.len, self.idx)
+            self._sample()
         ops.counter_add(self.len, 1)
 
     # -- phase 2: the sliding window -------------------------------------------------------
@@ -172,7 +190,7 @@ class DecodeEngine:
         Fn.linear_fwd(o, self._w(f"{l}.proj_w"), x3, "bias_resid", bias=self._b(f"{l}.proj_b"), resid=xl)
         x4 = self._ffn_tail(l, x3)
         self._head(x4)
-        ops.decode_sample(self.logits, self.greedy, self.seed, self.len, self.idx)
+        self._sample()
         ops.counter_add(self.len, 1)
 
     # -- driver ------------------------------------------------------------------------------
@@ -193,11 +211,19 @@ class DecodeEngine:
         return g
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, seed=None):
+    def generate(self, idx, max_new_tokens, seed=None, sampling=None):
+        """``sampling``: (temperature, top_k, top_p) for a filtered engine -- written to the device
+        buffer the sampler reads, so every setting replays the same graphs; None keeps the last."""
         B, L0 = idx.shape
+        if sampling is not None:
+            if not self.filtered:
+                raise ValueError("DecodeEngine: sampling=(temperature, top_k, top_p) needs an engine built with filtered=True")
+            check_sampling(*sampling)
         if B != self.B or L0 < 1 or L0 + max_new_tokens > self.max_len:
             raise ValueError(f"DecodeEngine(batch={self.B}, max_len={self.max_len}) cannot run idx {tuple(idx.shape)} "
                              f"+ {max_new_tokens} tokens")
+        if sampling is not None:
+            self.params.copy_(sampling_params(*sampling))
         was_training = self.m.training
         self.m.eval()
         try:

@@ -28,6 +28,7 @@ from .data import DEFAULT_INPUT, BatchSampler, TokenStream
 from .engine import Evaluator, TrainStep
 from .model import BigramLanguageModel
 from .optim import AdamW
+from .sampling import add_sampling_args
 
 
 @torch.no_grad()
@@ -62,6 +63,7 @@ def parse_args(argv=None):
     ap.add_argument("--dropout", type=float)
     ap.add_argument("--lr", type=float, help="optimizer lr (GPT1.py:218 uses 5e-1; its learning_rate = 2e-4 is unused)")
     ap.add_argument("--max-new-tokens", type=int, default=500)
+    add_sampling_args(ap)   # --temperature / --top-k / --top-p of the final sample; neutral defaults (GPT1.py:236)
     ap.add_argument("--out", default="model.pth", help="state dict file (GPT1.py:240); '' to skip")
     ap.add_argument("--save-checkpoint", default=None, help="also write a resumable training checkpoint")
     ap.add_argument("--resume", default=None, help="continue from a --save-checkpoint file")
@@ -98,7 +100,8 @@ def main(argv=None):
     if a.save_checkpoint:
         checkpoint.save_checkpoint(a.save_checkpoint, m, optimizer, cfg.max_iters)
     context = torch.zeros((1, 1), dtype=torch.long, device=device)            # GPT1.py:235
-    print(tok.decode(m.generate(context, max_new_tokens=a.max_new_tokens)[0].tolist()))   # GPT1.py:236
+    print(tok.decode(m.generate(context, max_new_tokens=a.max_new_tokens, temperature=a.temperature, top_k=a.top_k,
+                                top_p=a.top_p)[0].tolist()))                  # GPT1.py:236
     if a.out:
         checkpoint.save_model(m, a.out)                                       # GPT1.py:239-241
     return m

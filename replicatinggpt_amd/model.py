@@ -513,7 +513,8 @@ class BigramLanguageModel(nn.Module):
         self._premasks = pm
 
     # -- generate (GPT1.py:196-212) ----------------------------------------------------
-    def generate(self, idx, max_new_tokens, greedy=False, generator=None, engine=True):
+    def generate(self, idx, max_new_tokens, greedy=False, generator=None, engine=True, temperature=1.0, top_k=None,
+                 top_p=1.0):
         """Autoregressive sampling as GPT1.py:196-212 (crop to block_size, forward, last row,
         softmax, multinomial, append).  On the GPU this runs the batched decode engine
         (decode.DecodeEngine: K/V-cached prefix phase, sliding-window phase, device sampling, one
@@ -521,18 +522,28 @@ class BigramLanguageModel(nn.Module):
         a seed taken from ``generator`` (torch's CPU multinomial stream is not reproducible on a
         GPU).  ``engine=False`` runs the reference's loop literally (one full forward per token); so
         does a model in train mode with dropout on, as GPT1.py:235-236 calls it: the
-        engine computes the eval-mode forward only."""
+        engine computes the eval-mode forward only.
+
+        ``temperature`` (> 0), ``top_k`` (0 / None: off) and ``top_p`` (in (0, 1]; 1: off) shape the
+        sampled distribution in HF's order -- temperature, top-k, then top-p on the renormalised top-k
+        distribution (sampling.py; the contract is cg_decode_sample_filtered's in include/charpt.h).
+        At their neutral defaults every path is the one described above, unchanged; any other value
+        selects an engine whose sampler reads the three settings from device memory, so changing them
+        between calls replays the same graphs."""
+        from .sampling import check_sampling, filter_logits
+        neutral = check_sampling(temperature, top_k, top_p, greedy)
         dropout_on = self.training and self.config.dropout > 0
         if engine and not dropout_on and idx.device.type == "cuda" and max_new_tokens > 0:
             from .decode import DecodeEngine
             B, L0 = idx.shape
-            key = (B, L0 + max_new_tokens, bool(greedy), idx.device)
+            key = (B, L0 + max_new_tokens, bool(greedy), not neutral, idx.device)
             cache = self.__dict__.setdefault("_decode_engines", {})
             eng = cache.get(key)
             if eng is None or eng.m is not self:
-                eng = cache[key] = DecodeEngine(self, B, L0 + max_new_tokens, greedy=greedy)
+                eng = cache[key] = DecodeEngine(self, B, L0 + max_new_tokens, greedy=greedy, filtered=not neutral)
             seed = None if greedy else int(torch.randint(0, 2 ** 62, (1,), generator=generator))
-            return eng.generate(idx, max_new_tokens, seed=seed)
+            return eng.generate(idx, max_new_tokens, seed=seed,
+                                sampling=None if neutral else (temperature, top_k, top_p))
         for _ in range(max_new_tokens):
             idx_cond = idx[:, -self.config.block_size:]                 # GPT1.py:200
             logits, _ = self(idx_cond)                                   # GPT1.py:202
@@ -540,6 +551,7 @@ class BigramLanguageModel(nn.Module):
             if greedy:
                 idx_next = torch.argmax(logits, dim=-1, keepdim=True)
             else:
+                logits = filter_logits(logits, temperature, top_k, top_p)   # neutral: logits itself
                 probs = F.softmax(logits, dim=-1)                        # GPT1.py:206
                 idx_next = torch.multinomial(probs, num_samples=1, generator=generator)  # GPT1.py:208
             idx = torch.cat((idx, idx_next), dim=1)                     # GPT1.py:210

@@ -487,6 +487,21 @@ def decode_sample(logits: Tensor, greedy: bool, seed: Tensor, len_dev: Tensor, i
                                       L.ptr(len_dev), L.ptr(idx), idx.stride(0), _s(logits)), "decode_sample")
 
 
+@_op("decode_sample_filtered", ("idx",))
+def decode_sample_filtered(logits: Tensor, params: Tensor, seed: Tensor, len_dev: Tensor, idx: Tensor) -> None:
+    """decode_sample's draw under a temperature, a top-k and a top-p cut (include/charpt.h
+    cg_decode_sample_filtered): params = three device floats (temperature, top_k or 0, top_p) read by
+    the kernel, so a captured graph serves every setting."""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("decode_sample_filtered: logits must be float32 [B, V] with unit column stride")
+    if params.dtype != torch.float32 or params.numel() < 3 or not params.is_contiguous():
+        raise ValueError("decode_sample_filtered: params must be three contiguous float32 (temperature, top_k, top_p)")
+    B, V = logits.shape
+    L.check(L.load().cg_decode_sample_filtered(L.ptr(logits), logits.stride(0), V, B, L.ptr(params), L.ptr(seed),
+                                               L.ptr(len_dev), L.ptr(idx), idx.stride(0), _s(logits)),
+            "decode_sample_filtered")
+
+
 # ---------------------------------------------------------------------------------------
 @_op("adamw", ("p", "m", "v", "p_bf16"))
 def adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, p_bf16: Optional[Tensor], lr: float, beta1: float, beta2: float,
