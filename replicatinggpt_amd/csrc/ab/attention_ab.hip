@@ -1,9 +1,59 @@
 // charpt A/B-only attention variants (never the product library: `make ab`, CG_AB_VARIANTS):
-// measured slower than the product kernels of attention_d64.h, kept for the interleaved A/B tools.
-#include "../attention_d64.h"
+// measured slower than the product kernels of attention_d64_ring.h, kept for the interleaved A/B tools.
+#include "../attention_d64_ring.h"
 
 namespace cg {
 namespace {
+// two [64][64] bf16 tiles (rows row0..row0+63 of X and Y) staged through registers: 4 x 16 B per thread
+struct Stage2 {
+    uint4 a0, a1, b0, b1;
+};
+__device__ __forceinline__ Stage2 stage_load(const bf16_t* X, int64_t ldx, const bf16_t* Y, int64_t ldy, int64_t row0,
+                                             int tid) {
+    const int r = tid >> 3, c = tid & 7;
+    Stage2 s;
+    s.a0 = *(const uint4*)(X + (row0 + r) * ldx + c * 8);
+    s.a1 = *(const uint4*)(X + (row0 + r + 32) * ldx + c * 8);
+    s.b0 = *(const uint4*)(Y + (row0 + r) * ldy + c * 8);
+    s.b1 = *(const uint4*)(Y + (row0 + r + 32) * ldy + c * 8);
+    return s;
+}
+__device__ __forceinline__ void stage_store(const Stage2& s, char* img, int tid) {
+    const int r = tid >> 3, c = tid & 7;
+    *(uint4*)(img + aoff(r, c)) = s.a0;
+    *(uint4*)(img + aoff(r + 32, c)) = s.a1;
+    *(uint4*)(img + TILE + aoff(r, c)) = s.b0;
+    *(uint4*)(img + TILE + aoff(r + 32, c)) = s.b1;
+}
+
+// one [64][64] bf16 tile staged through registers: 2 x 16 B per thread
+struct Stage1 {
+    uint4 a0, a1;
+};
+__device__ __forceinline__ Stage1 stage_load1(const bf16_t* X, int64_t ldx, int64_t row0, int tid) {
+    const int r = tid >> 3, c = tid & 7;
+    return Stage1{*(const uint4*)(X + (row0 + r) * ldx + c * 8), *(const uint4*)(X + (row0 + r + 32) * ldx + c * 8)};
+}
+__device__ __forceinline__ void stage_store1(const Stage1& s, char* img, int tid) {
+    const int r = tid >> 3, c = tid & 7;
+    *(uint4*)(img + aoff(r, c)) = s.a0;
+    *(uint4*)(img + aoff(r + 32, c)) = s.a1;
+}
+
+// Forward.  Tiles where both of a wave's query groups (A = 7 - w, B = w) are full (before B's
+// diagonal tile) run software-pipelined, B one phase behind A, so every MFMA phase has the other
+// group's softmax VALU work beside it:
+//   [1] S_A(kv)      || P_B(kv-1) = softmax of B's previous tile
+//   [2] O_B += P_B V(kv-1) || max_A(kv), A's rescale decision
+//   [3] S_B(kv)      || P_A(kv)
+//   [4] O_A += P_A V(kv)   || max_B(kv), B's rescale decision
+// (each group's decision precedes its exponentials and follows its previous P V).  K/V tiles go
+// through a 3-slot LDS ring (B still reads V(kv-1) while kv+1 is written), one barrier per tile.
+// The diagonal and later tiles run unpipelined.  The block's 256 Q rows live in LDS (32 KB, same
+// swizzle) rather than in registers: 48 + 32 KB per block, two blocks per CU.
+constexpr int FWD_SLOT = 2 * TILE;
+constexpr int FWD_LDS = 3 * FWD_SLOT + 4 * TILE;   // K/V ring + Q image: 80 KB
+
 template <bool DROP>
 __device__ __forceinline__ void fwd_qblock(int qblk, int bh, char* smem, int64_t T_, int H, const bf16_t* __restrict__ q,
                                            const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int64_t ld,
@@ -375,44 +425,30 @@ __global__ __launch_bounds__(512, 1) void k_attn_fwd_pp(int64_t T_, int H, const
 namespace attn_ab {
 bool launch_fwd(int variant, dim3 grid, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v,
                 int64_t ld, bf16_t* o, int64_t ldo, float* lse, float scale, const DropArgs& d, hipStream_t st) {
-    if (variant == 5) {   // the register-staged ring with the Q image in LDS
-        if (d.mask)
-            k_attn_fwd_d64<true><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, lse, scale * LOG2E, d.mask, d.dscale);
-        else
-            k_attn_fwd_d64<false><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, lse, scale * LOG2E, nullptr, 1.f);
-        return true;
-    }
-    if (variant == 6) {   // Q image in LDS, 3-slot DMA ring one tile ahead
-        if (d.mask)
-            k_attn_fwd_d64d<true, false><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, lse, scale * LOG2E, d.mask,
+    const bool pp = variant == 4 && T % 256 == 0 && T >= 512 && T <= 64 * PP_KW_TILES;
+    if (variant != 5 && variant != 6 && !pp) return false;
+    with_drop(d, [&](auto drop) {
+        constexpr bool DROP = decltype(drop)::value;
+        if (variant == 5)   // the register-staged ring with the Q image in LDS
+            k_attn_fwd_d64<DROP><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, lse, scale * LOG2E, d.mask, d.dscale);
+        else if (variant == 6)   // Q image in LDS, 3-slot DMA ring one tile ahead
+            k_attn_fwd_d64d<DROP, false><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, lse, scale * LOG2E, d.mask,
                                                                d.dscale);
-        else
-            k_attn_fwd_d64d<false, false><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, lse, scale * LOG2E,
-                                                                nullptr, 1.f);
-        return true;
-    }
-    if (variant == 4 && T % 256 == 0 && T >= 512 && T <= 64 * PP_KW_TILES) {   // the 8-wave ping-pong forward
-        if (d.mask)
-            k_attn_fwd_pp<true><<<grid, 512, PP_LDS, st>>>(T, H, q, k, v, ld, o, ldo, lse, scale * LOG2E, d.mask,
+        else   // the 8-wave ping-pong forward
+            k_attn_fwd_pp<DROP><<<grid, 512, PP_LDS, st>>>(T, H, q, k, v, ld, o, ldo, lse, scale * LOG2E, d.mask,
                                                           d.dscale);
-        else
-            k_attn_fwd_pp<false><<<grid, 512, PP_LDS, st>>>(T, H, q, k, v, ld, o, ldo, lse, scale * LOG2E, nullptr,
-                                                           1.f);
-        return true;
-    }
-    return false;
+    });
+    return true;
 }
 
 bool launch_dq(int variant, dim3 grid, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v,
                int64_t ld, const bf16_t* o, int64_t ldo, const bf16_t* dout, int64_t ldd, const float* lse,
                float* delta, bf16_t* dq, int64_t lddq, float scale, const DropArgs& d, hipStream_t st) {
     if (variant != 7) return false;   // the 2-slot ring one tile ahead
-    if (d.mask)
-        k_attn_dq_d64<true, 2><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, dout, ldd, lse, delta, dq, lddq, scale,
-                                                     d.mask, d.dscale);
-    else
-        k_attn_dq_d64<false, 2><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, dout, ldd, lse, delta, dq, lddq, scale,
-                                                      nullptr, 1.f);
+    with_drop(d, [&](auto drop) {
+        k_attn_dq_d64<decltype(drop)::value, 2><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, dout, ldd, lse, delta,
+                                                                       dq, lddq, scale, d.mask, d.dscale);
+    });
     return true;
 }
 
@@ -420,12 +456,10 @@ bool launch_dkdv(int variant, dim3 grid, int64_t T, int H, const bf16_t* q, cons
                  int64_t ld, const bf16_t* dout, int64_t ldd, const float* lse, const float* delta, bf16_t* dk,
                  bf16_t* dv, int64_t lddkv, float scale, const DropArgs& d, hipStream_t st) {
     if (variant != 7) return false;   // the 2-slot ring one tile ahead
-    if (d.mask)
-        k_attn_dkdv_d64<true, 2><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, dout, ldd, lse, delta, dk, dv, lddkv, scale,
-                                                       d.mask_bwd, d.dscale);
-    else
-        k_attn_dkdv_d64<false, 2><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, dout, ldd, lse, delta, dk, dv, lddkv,
-                                                        scale, nullptr, 1.f);
+    with_drop(d, [&](auto drop) {
+        k_attn_dkdv_d64<decltype(drop)::value, 2><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, dout, ldd, lse, delta, dk, dv,
+                                                                         lddkv, scale, d.mask_bwd, d.dscale);
+    });
     return true;
 }
 }  // namespace attn_ab

@@ -1,0 +1,122 @@
+// charpt: the attention C ABI and its dispatch among the kernel families (attention_common.h):
+// the bf16 MFMA kernels for head_size 64 (attention_d64.hip), the fp32 MFMA forward for small heads
+// (attention_f32.hip) and the generic kernels (attention_generic.hip); the keep bits of the MFMA
+// path come from attention_dropmask.hip.  Head.forward x n_head, GPT1.py:109-123,134-135.
+#include "attention_common.h"
+
+using namespace cg;
+
+namespace {
+
+bool fast_attn_ok(int dtype, int64_t T, int64_t D, const void* a, const void* b, const void* c, int64_t ld1,
+                  int64_t ld2) {
+    return dtype == CG_BF16 && D == 64 && T % 64 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0 &&
+           ld1 % 8 == 0 && ld2 % 8 == 0;
+}
+
+// the backward workspace: delta = rowsum(dO * O) rounded up to 256 B, then a keep-bit image
+int64_t delta_bytes(int64_t B, int64_t T, int64_t H) { return (B * H * T * (int64_t)sizeof(float) + 255) / 256 * 256; }
+
+int attn_fwd_impl(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const void* q, const void* k, const void* v,
+                  int64_t ld_qkv, void* o, int64_t ld_o, float* lse, float scale, double dropout_p, uint64_t seed,
+                  const uint64_t* rng_call, int site, uint64_t* mask, bool mask_ready, void* stream) {
+    CG_REQUIRE(B > 0 && T > 0 && H > 0 && D > 0 && D <= 128, "cg_attn_fwd: bad shape (D must be <= 128)");
+    CG_REQUIRE(dropout_p >= 0 && dropout_p < 1, "cg_attn_fwd: dropout_p must be in [0,1)");
+    hipStream_t st = (hipStream_t)stream;
+    DropArgs d = attn::make_drop(dropout_p, seed, rng_call, site);
+    if (fast_attn_ok(dtype, T, D, q, k, o, ld_qkv, ld_o)) {
+        if (d.thr) {
+            CG_REQUIRE(mask, "cg_attn_fwd: dropout on the MFMA path needs a mask buffer (cg_attn_mask_bytes)");
+            if (!mask_ready) attn::launch_dropmask(B, H, T, mask, d, st);
+            attn::set_masks(d, mask, B, H, T);
+        }
+        attn::launch_fwd_d64(B, T, (int)H, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld_qkv, (bf16_t*)o,
+                             ld_o, lse, scale, d, st);
+    } else if (dtype == CG_F32 && !d.thr && D <= 32) {
+        attn::launch_fwd_f32(B, T, (int)H, (int)D, (const float*)q, (const float*)k, (const float*)v, ld_qkv, (float*)o,
+                             ld_o, lse, scale, st);
+    } else {
+        attn::launch_fwd_generic(dtype, B, T, (int)H, (int)D, q, k, v, ld_qkv, o, ld_o, lse, scale, d, st);
+    }
+    CG_LAUNCH_CHECK("cg_attn_fwd");
+    return CG_OK;
+}
+
+// delta_in: rowsum(dO * O) precomputed (cg_attn_bwd_delta), read only by the merged resident kernel
+int attn_bwd_impl(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const void* q, const void* k,
+                  const void* v, int64_t ld_qkv, const void* o, int64_t ld_o, const void* dout, int64_t ld_do,
+                  const float* lse, const float* delta_in, void* dq, void* dk, void* dv, int64_t ld_dqkv, float scale,
+                  double dropout_p, uint64_t seed, const uint64_t* rng_call, int site, const uint64_t* mask,
+                  void* workspace, void* stream) {
+    CG_REQUIRE(B > 0 && T > 0 && H > 0 && D > 0 && D <= 128, "cg_attn_bwd: bad shape (D must be <= 128)");
+    CG_REQUIRE(workspace, "cg_attn_bwd: workspace required");
+    hipStream_t st = (hipStream_t)stream;
+    DropArgs d = attn::make_drop(dropout_p, seed, rng_call, site);
+    float* delta = (float*)workspace;
+    const bool fast = fast_attn_ok(dtype, T, D, q, dout, dq, ld_qkv, ld_do) && ld_dqkv % 8 == 0 &&
+                      ((((uintptr_t)dk) | ((uintptr_t)dv) | ((uintptr_t)o)) & 15) == 0 && ld_o % 8 == 0;
+    if (fast) {
+        // delta = rowsum(dO * O) is computed inside the dQ kernel (which runs before dK/dV)
+        if (d.thr) {
+            if (!mask) {  // regenerate the forward's keep bits (identical Philox stream)
+                uint64_t* m = (uint64_t*)((char*)workspace + delta_bytes(B, T, H));
+                attn::launch_dropmask(B, H, T, m, d, st);
+                mask = m;
+            }
+            attn::set_masks(d, mask, B, H, T);
+        }
+        const bf16_t *Q = (const bf16_t*)q, *K = (const bf16_t*)k, *V = (const bf16_t*)v, *DO = (const bf16_t*)dout;
+        const bool din = delta_in && attn::bwd_merged(T);
+        attn::launch_bwd_d64(B, T, (int)H, Q, K, V, ld_qkv, (const bf16_t*)o, ld_o, DO, ld_do, lse,
+                             din ? (float*)delta_in : delta, din, (bf16_t*)dq, ld_dqkv, (bf16_t*)dk, (bf16_t*)dv,
+                             ld_dqkv, scale, d, st);
+    } else {
+        attn::launch_bwd_generic(dtype, B, T, (int)H, (int)D, q, k, v, ld_qkv, o, ld_o, dout, ld_do, lse, delta, dq, dk,
+                                 dv, ld_dqkv, scale, d, st);
+    }
+    CG_LAUNCH_CHECK("cg_attn_bwd");
+    return CG_OK;
+}
+
+}  // namespace
+
+extern "C" int cg_attn_fwd(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const void* q, const void* k,
+                           const void* v, int64_t ld_qkv, void* o, int64_t ld_o, float* lse, float scale,
+                           double dropout_p, uint64_t seed, const uint64_t* rng_call, int site, uint64_t* mask,
+                           void* stream) {
+    return attn_fwd_impl(dtype, B, T, H, D, q, k, v, ld_qkv, o, ld_o, lse, scale, dropout_p, seed, rng_call, site,
+                         mask, false, stream);
+}
+
+extern "C" int cg_attn_fwd_premasked(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const void* q,
+                                     const void* k, const void* v, int64_t ld_qkv, void* o, int64_t ld_o, float* lse,
+                                     float scale, double dropout_p, uint64_t seed, const uint64_t* rng_call, int site,
+                                     uint64_t* mask, void* stream) {
+    return attn_fwd_impl(dtype, B, T, H, D, q, k, v, ld_qkv, o, ld_o, lse, scale, dropout_p, seed, rng_call, site,
+                         mask, true, stream);
+}
+
+extern "C" int64_t cg_attn_bwd_workspace(int64_t B, int64_t T, int64_t H, int64_t D) {
+    (void)D;
+    return delta_bytes(B, T, H) + attn::mask_bytes(B, H, T);
+}
+
+extern "C" int cg_attn_bwd(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const void* q, const void* k,
+                           const void* v, int64_t ld_qkv, const void* o, int64_t ld_o, const void* dout, int64_t ld_do,
+                           const float* lse, void* dq, void* dk, void* dv, int64_t ld_dqkv, float scale,
+                           double dropout_p, uint64_t seed, const uint64_t* rng_call, int site, const uint64_t* mask,
+                           void* workspace, void* stream) {
+    return attn_bwd_impl(dtype, B, T, H, D, q, k, v, ld_qkv, o, ld_o, dout, ld_do, lse, nullptr, dq, dk, dv, ld_dqkv,
+                         scale, dropout_p, seed, rng_call, site, mask, workspace, stream);
+}
+
+extern "C" int cg_attn_bwd_delta(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const void* q, const void* k,
+                                 const void* v, int64_t ld_qkv, const void* o, int64_t ld_o, const void* dout,
+                                 int64_t ld_do, const float* lse, const float* delta, void* dq, void* dk, void* dv,
+                                 int64_t ld_dqkv, float scale, double dropout_p, uint64_t seed,
+                                 const uint64_t* rng_call, int site, const uint64_t* mask, void* workspace,
+                                 void* stream) {
+    CG_REQUIRE(!delta || (((uintptr_t)delta) & 3) == 0, "cg_attn_bwd_delta: delta must be 4-byte aligned");
+    return attn_bwd_impl(dtype, B, T, H, D, q, k, v, ld_qkv, o, ld_o, dout, ld_do, lse, delta, dq, dk, dv, ld_dqkv,
+                         scale, dropout_p, seed, rng_call, site, mask, workspace, stream);
+}

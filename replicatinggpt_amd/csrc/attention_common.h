@@ -1,6 +1,10 @@
-// charpt attention internals shared by attention_generic.hip (generic kernels, dropout mask,
-// C ABI) and attention_d64.hip (bf16 MFMA kernels for head_size 64).
+// charpt attention internals shared by attention.hip (the C ABI and the dispatch) and the kernel
+// families it launches, each through the host launchers declared here: attention_dropmask.hip (keep
+// bits), attention_f32.hip (fp32 MFMA forward), attention_generic.hip (fp32-math VALU kernels) and
+// attention_d64.hip (bf16 MFMA kernels for head_size 64).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace cg {
@@ -45,14 +49,44 @@ __device__ __forceinline__ int64_t mask_bwd_tile(int kb, int qt, int np) {
 // all-ones where bit `bit` of a lane's mask word is set (one v_bfe_i32)
 __device__ __forceinline__ uint32_t keep_lanes(uint32_t w, int bit) { return (uint32_t)((int32_t)(w << (31 - bit)) >> 31); }
 
+// f(std::bool_constant<flag>): a run-time flag as a kernel's compile-time template argument
+template <typename F>
+inline void with_flag(bool flag, F&& f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+// DROP of the bf16 MFMA kernels.  Without dropout make_drop leaves d.mask = d.mask_bwd = nullptr and
+// d.dscale = 1.f, so the launch sites pass them unconditionally.
+template <typename F>
+inline void with_drop(const DropArgs& d, F&& f) {
+    with_flag(d.mask != nullptr, f);
+}
+
 namespace attn {
+// keep bits (attention_dropmask.hip).  make_drop: the arguments of dropout probability p, no keep-bit
+// image yet (mask = mask_bwd = nullptr); mask_bytes: the image's size, FWD and BWD tiles;
+// launch_dropmask: generate it into `mask`; set_masks: point d at a generated image
+DropArgs make_drop(double p, uint64_t seed, const uint64_t* rng_call, int site);
+int64_t mask_bytes(int64_t B, int64_t H, int64_t T);
+void set_masks(DropArgs& d, const uint64_t* mask, int64_t B, int64_t H, int64_t T);
+void launch_dropmask(int64_t B, int64_t H, int64_t T, uint64_t* mask, const DropArgs& d, hipStream_t st);
+
+// fp32 MFMA forward, D <= 32, no dropout (attention_f32.hip): sequence-resident at T <= 256
+void launch_fwd_f32(int64_t B, int64_t T, int H, int D, const float* q, const float* k, const float* v, int64_t ld,
+                    float* o, int64_t ldo, float* lse, float scale, hipStream_t st);
+
+// fp32-math VALU kernels, any D <= 128 and any T, dtype CG_BF16 or CG_F32 (attention_generic.hip); the
+// backward computes delta = rowsum(dO * O) into `delta` first
+void launch_fwd_generic(int dtype, int64_t B, int64_t T_, int H, int D, const void* q, const void* k, const void* v,
+                        int64_t ld, void* o, int64_t ldo, float* lse, float scale, const DropArgs& d, hipStream_t st);
+void launch_bwd_generic(int dtype, int64_t B, int64_t T_, int H, int D, const void* q, const void* k, const void* v,
+                        int64_t ld, const void* o, int64_t ldo, const void* dout, int64_t ldd, const float* lse,
+                        float* delta, void* dq, void* dk, void* dv, int64_t lddqkv, float scale, const DropArgs& d,
+                        hipStream_t st);
+
 // bf16 MFMA kernels, head_size 64, T % 64 == 0 (attention_d64.hip)
 void launch_fwd_d64(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld,
                     bf16_t* o, int64_t ldo, float* lse, float scale, const DropArgs& d, hipStream_t st);
-// also computes delta = rowsum(dO * O) for its queries and writes it (read by launch_dkdv_d64 next)
-void launch_dq_d64(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld,
-                   const bf16_t* o, int64_t ldo, const bf16_t* dout, int64_t ldd, const float* lse, float* delta,
-                   bf16_t* dq, int64_t lddq, float scale, const DropArgs& d, hipStream_t st);
 // dQ then dK/dV (T <= 256: one merged launch, bwd_merged(T)); delta_ready (merged launch only):
 // `delta` already holds rowsum(dO * O) and is read, not computed
 bool bwd_merged(int64_t T);
@@ -60,9 +94,6 @@ void launch_bwd_d64(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* 
                     const bf16_t* o, int64_t ldo, const bf16_t* dout, int64_t ldd, const float* lse, float* delta,
                     bool delta_ready, bf16_t* dq, int64_t lddq, bf16_t* dk, bf16_t* dv, int64_t lddkv, float scale, const DropArgs& d,
                     hipStream_t st);
-void launch_dkdv_d64(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld,
-                     const bf16_t* dout, int64_t ldd, const float* lse, const float* delta, bf16_t* dk, bf16_t* dv,
-                     int64_t lddkv, float scale, const DropArgs& d, hipStream_t st);
 }  // namespace attn
 // cg_set_tuning knobs (attention_d64.hip)
 extern int g_attn_variant;

@@ -1,5 +1,5 @@
 // charpt: the LayerNorm forward's row body (nn.LayerNorm, GPT1.py:159-160,173), shared by
-// layernorm.hip's k_ln_fwd and the LayerNorm + attention keep-bit launch (attention_generic.hip
+// layernorm.hip's k_ln_fwd and the LayerNorm + attention keep-bit launch (attention_dropmask.hip
 // k_ln_fwd_dropmask).
 #pragma once
 #include "common.h"

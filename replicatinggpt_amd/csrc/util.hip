@@ -281,11 +281,12 @@ const Knob KNOBS[] = {
     {"adam_per_launch", &g_adam_per_launch, ANY_LO, ANY_HI},   // defer.hip: AdamW jobs per launch's free blocks
     {"adam_batch", &g_adam_batch, AB_LO(1), AB_HI(1)},   // defer.hip: side-block AdamW chunks in flight (A/B: 4, 5)
     {"red_side", &g_red_side, ANY_LO, ANY_HI},     // defer.hip: part-filling launches take a pending reduce on extra blocks
-    // attention_d64.hip: 0 automatic, 1 ring kernels at T <= 256 (and the 64-query-block fp32 forward instead of
-    // the sequence-resident one), 2 separate resident dQ / dK-dV launches (A/B build also 4: the 8-wave
-    // ping-pong forward at T % 256 == 0, 512..1024)
+    // attention_d64.hip: 0 automatic, 1 ring kernels at T <= 256 (and, attention_f32.hip, the 64-query-block
+    // fp32 forward instead of the sequence-resident one), 2 separate resident dQ / dK-dV launches (A/B
+    // build, ab/attention_ab.hip, also 4: the 8-wave ping-pong forward at T % 256 == 0, 512..1024; 5 / 6:
+    // the earlier forward rings; 7: the 2-slot backward rings)
     {"attn_variant", &g_attn_variant, AB_LO(0), AB_HI(2)},
-    {"attn_bwd_lpt", &g_attn_bwd_lpt, 0, 1},       // attention_d64.hip: merged resident backward order (1 = dK/dV first)
+    {"attn_bwd_lpt", &g_attn_bwd_lpt, 0, 1},       // attention_d64.hip k_attn_bwd_d64r: merged resident backward order (1 = dK/dV first)
     {"decode_attn_rows", &g_decode_attn_rows, 0, 1},   // decode.hip: the coalesced-chunk phase-1 decode attention
     {"adamw_mode", &g_adamw_mode, 0, 5},           // ce_adamw.hip: cg_adamw's kernel form, 0 = by size
     {"ln_rl", &g_ln_rl, 0, 2},   // layernorm.hip: backward rows' next loads before the current stores (2: also at C = 768)

@@ -787,7 +787,7 @@ def test_gemm_store_rowdot(M, C, T):
         O.gemm_store_rowdot(dy1, w, do1, 1000, C, C, C, C, C, o1, C, 200, delta)
 
 
-@pytest.mark.parametrize("T", [256, 192, 64])
+@pytest.mark.parametrize("T", [256, 192, 128, 64])
 @pytest.mark.parametrize("p", [0.0, 0.2])
 def test_attention_bwd_precomputed_delta(T, p):
     """cg_attn_bwd_delta: the merged resident backward reading delta instead of loading O.  Given the

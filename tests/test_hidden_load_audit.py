@@ -29,7 +29,7 @@ def _makefile():
 
 
 def _text_with_local_headers(src):
-    """the source and the csrc headers it includes (the kernels may live in a header: attention_d64.h)"""
+    """the source and the csrc headers it includes (the kernels may live in headers: attention_d64_ring.h, attention_d64_res.h)"""
     text = open(os.path.join(CSRC, src)).read()
     for h in re.findall(r'^#include "([^"]+)"', text, re.M):
         if os.path.exists(os.path.join(CSRC, h)) and not h.endswith("common.h"):
