@@ -408,6 +408,28 @@ int cg_adamw_defer(float* p, const float* g, float* m, float* v, uint16_t* p_bf1
 int cg_adamw_segments(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, const int64_t* segs, int nseg,
                       double lr, double beta1, double beta2, double eps, double weight_decay,
                       const int64_t* step_ptr, void* stream);
+/* cg_adamw with the learning rate read from the device when the kernel runs (*lr_dev, a double: a
+   schedule that happens to be constant gives cg_adamw's bits), so a captured graph follows a
+   schedule.  gscale_dev != NULL: every gradient is g * *gscale_dev rounded once to fp32 before the
+   update (g itself is not written) -- the bits of cg_scale_f32 on g followed by cg_adamw, without
+   that pass.  NULL: no multiply.  The same kernel forms by size as cg_adamw.  The GEMM-hosted
+   updates (cg_adamw_defer) and cg_adamw_segments have no device-lr form yet.                   */
+int cg_adamw_dyn(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, const double* lr_dev,
+                 const float* gscale_dev, double beta1, double beta2, double eps, double weight_decay,
+                 const int64_t* step_ptr, void* stream);
+
+/* ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) ------------
+   out[0] = ||g||_2 over n floats = (float)sqrt(sum of squares accumulated in fp64), out[1] = the
+   clip coefficient min(1, max_norm / (out[0] + 1e-6)) in fp32 (one add, one correctly rounded
+   divide: torch's formula).  One read pass, two launches (per-block partials in `workspace`, then an
+   ordered fold): the grid depends only on n and every fold has a fixed order, so the result is
+   bit-identical run to run and on every rank that holds the same gradients.  g: any 4-B alignment
+   (16-B loads from the first 16-B boundary), any n; n == 0: norm 0.  +inf in g: (inf, 0).  NaN in g:
+   a NaN norm, coefficient 1.  workspace: cg_grad_norm_workspace(n) bytes, 8-B aligned.             */
+int64_t cg_grad_norm_workspace(int64_t n);
+int cg_grad_norm(const float* g, int64_t n, float max_norm, float* out, void* workspace, void* stream);
+/* x[i] *= *scale_dev for i in [0, n) (clip_grad_norm_'s in-place scale, for hand-written loops) */
+int cg_scale_f32(float* x, int64_t n, const float* scale_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,10 @@ _SIGS = {
     "cg_adamw": (c_int, [P, P, P, P, P, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, P, P]),
     "cg_adamw_defer": (c_int, [P, P, P, P, P, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, P, P]),
     "cg_adamw_segments": (c_int, [P, P, P, P, P, P, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, P, P]),
+    "cg_adamw_dyn": (c_int, [P, P, P, P, P, c_i64, P, P, c_dbl, c_dbl, c_dbl, c_dbl, P, P]),
+    "cg_grad_norm_workspace": (c_i64, [c_i64]),
+    "cg_grad_norm": (c_int, [P, c_i64, c_flt, P, P, P]),
+    "cg_scale_f32": (c_int, [P, c_i64, P, P]),
     "cg_timing_event_create": (c_int, [ctypes.POINTER(P)]),
     "cg_timing_event_record": (c_int, [P, P]),
     "cg_timing_event_elapsed": (c_int, [P, P, ctypes.POINTER(c_flt)]),

@@ -2,6 +2,8 @@
 // the fused AdamW step over flat fp32 buffers (torch.optim.AdamW, GPT1.py:218,233).
 #include <math.h>
 
+#include <type_traits>
+
 #include "adamw.h"
 #include "common.h"
 #include "defer.h"
@@ -88,14 +90,48 @@ __device__ __forceinline__ void st4(float* p, float4 x) {
 }
 
 
+// The learning-rate argument of k_adamw.  DYN = false (cg_adamw): the host's double, the kernel
+// argument it always was.  DYN = true (cg_adamw_dyn): device pointers read when the kernel runs, so a
+// captured graph follows a schedule -- the learning rate as a double (a schedule that happens to be
+// constant gives adam_scalars the host path's bits) and, when gscale != NULL, the gradient-clip
+// coefficient every gradient is multiplied by first.
+struct AdamLrDev {
+    const double* lr;
+    const float* gscale;
+};
+template <bool DYN>
+using AdamLr = std::conditional_t<DYN, AdamLrDev, double>;
+
+__device__ __forceinline__ double adam_lr(double lr) { return lr; }
+__device__ __forceinline__ double adam_lr(const AdamLrDev& a) { return *a.lr; }
+
+// g * c rounded once to fp32 (never contracted into adam_one's g - m): the bits of scaling the
+// gradient buffer in place (cg_scale_f32) before the update
+// (a select, not a branch: a branch between the load groups would end the batch of loads in flight)
+__device__ __forceinline__ float scaled_grad(float g, bool on, float c) {
+#pragma clang fp contract(off)
+    const float s = g * c;
+    return on ? s : g;
+}
+__device__ __forceinline__ float4 scaled_grad4(float4 g, bool on, float c) {
+    return make_float4(scaled_grad(g.x, on, c), scaled_grad(g.y, on, c), scaled_grad(g.z, on, c),
+                       scaled_grad(g.w, on, c));
+}
+
 // U float4 groups per thread per iteration (all loads issued before any arithmetic); NT: the
 // 30 B/param stream bypasses the caches (non-temporal loads and stores) -- every byte is touched once
-template <bool VEC, bool NT, int U>
+template <bool VEC, bool NT, int U, bool DYN>
 __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const float* __restrict__ g,
                                                float* __restrict__ m, float* __restrict__ v, bf16_t* __restrict__ pb,
-                                               int64_t n, double lr, double beta1, double beta2, double eps,
+                                               int64_t n, AdamLr<DYN> a, double beta1, double beta2, double eps,
                                                double wd, const int64_t* __restrict__ step_ptr) {
-    const AdamScalars s = adam_scalars(lr, beta1, beta2, eps, wd, step_ptr);
+    bool clip = false;
+    float coef = 1.f;
+    if constexpr (DYN) {
+        clip = a.gscale != nullptr;
+        if (clip) coef = *a.gscale;
+    }
+    const AdamScalars s = adam_scalars(adam_lr(a), beta1, beta2, eps, wd, step_ptr);
     const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
     int64_t i = i0;
@@ -113,6 +149,7 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t j = i + u * stride;
+                if constexpr (DYN) gv[u] = scaled_grad4(gv[u], clip, coef);
                 pv[u].x = adam_one(pv[u].x, gv[u].x, mv[u].x, vv[u].x, s);
                 pv[u].y = adam_one(pv[u].y, gv[u].y, mv[u].y, vv[u].y, s);
                 pv[u].z = adam_one(pv[u].z, gv[u].z, mv[u].z, vv[u].z, s);
@@ -131,6 +168,7 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
     for (; i < n; i += stride) {
         if (VEC && i + 3 < n) {
             float4 pv = ld4<NT>(p + i), gv = ld4<NT>(g + i), mv = ld4<NT>(m + i), vv = ld4<NT>(v + i);
+            if constexpr (DYN) gv = scaled_grad4(gv, clip, coef);
             pv.x = adam_one(pv.x, gv.x, mv.x, vv.x, s);
             pv.y = adam_one(pv.y, gv.y, mv.y, vv.y, s);
             pv.z = adam_one(pv.z, gv.z, mv.z, vv.z, s);
@@ -142,7 +180,10 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
         } else {
             for (int64_t j = i; j < n && j < i + 4; ++j) {
                 float mm = m[j], vv = v[j];
-                const float np = adam_one(p[j], g[j], mm, vv, s);
+                const float pj = p[j];
+                float gj = g[j];
+                if constexpr (DYN) gj = scaled_grad(gj, clip, coef);
+                const float np = adam_one(pj, gj, mm, vv, s);
                 p[j] = np;
                 m[j] = mm;
                 v[j] = vv;
@@ -162,7 +203,8 @@ namespace cg {
 int g_adamw_mode = 0;
 }
 
-static int adamw_launch(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, double lr,
+template <bool DYN>
+static int adamw_launch(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, AdamLr<DYN> lr,
                         double beta1, double beta2, double eps, double weight_decay, const int64_t* step_ptr,
                         void* stream) {
     CG_REQUIRE(n >= 0, "cg_adamw: n < 0");
@@ -174,9 +216,9 @@ static int adamw_launch(float* p, const float* g, float* m, float* v, uint16_t* 
     int grid = ceil_div((n + 3) / 4, 256);
     grid = grid > 8192 ? 8192 : grid;
     hipStream_t st = (hipStream_t)stream;
-#define ADAMW(VEC_, NT_, U_)                                                                                \
-    k_adamw<VEC_, NT_, U_><<<grid, 256, 0, st>>>(p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, \
-                                                 weight_decay, step_ptr)
+#define ADAMW(VEC_, NT_, U_)                                                                                     \
+    k_adamw<VEC_, NT_, U_, DYN><<<grid, 256, 0, st>>>(p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, \
+                                                      weight_decay, step_ptr)
     const int mode = g_adamw_mode ? g_adamw_mode : (n >= (int64_t)1 << 25 ? 2 : 1);
     if (!vec) ADAMW(false, false, 1);
     else if (mode == 2) ADAMW(true, true, 2);
@@ -267,12 +309,24 @@ int cg::adamw_segments_launch(float* p, const float* g, float* m, float* v, bf16
 
 namespace cg {
 int adamw_job_launch(const AdamJob& j, hipStream_t st) {
-    return adamw_launch(j.p, j.g, j.m, j.v, (uint16_t*)j.pb, 4 * j.n4, j.lr, j.beta1, j.beta2, j.eps, j.wd, j.step, st);
+    return adamw_launch<false>(j.p, j.g, j.m, j.v, (uint16_t*)j.pb, 4 * j.n4, j.lr, j.beta1, j.beta2, j.eps, j.wd,
+                               j.step, st);
 }
 }  // namespace cg
 
 extern "C" int cg_adamw(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, double lr,
                         double beta1, double beta2, double eps, double weight_decay, const int64_t* step_ptr,
                         void* stream) {
-    return adamw_launch(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step_ptr, stream);
+    return adamw_launch<false>(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step_ptr, stream);
+}
+
+// cg_adamw with the learning rate (and, optionally, a gradient scale) read from the device when the
+// kernel runs; the same kernel forms by size
+extern "C" int cg_adamw_dyn(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n,
+                            const double* lr_dev, const float* gscale_dev, double beta1, double beta2, double eps,
+                            double weight_decay, const int64_t* step_ptr, void* stream) {
+    CG_REQUIRE(lr_dev && (((uintptr_t)lr_dev) & 7) == 0 && (((uintptr_t)gscale_dev) & 3) == 0,
+               "cg_adamw_dyn: lr_dev must be a device double (8-B aligned), gscale_dev NULL or a device float");
+    return adamw_launch<true>(p, g, m, v, p_bf16, n, {lr_dev, gscale_dev}, beta1, beta2, eps, weight_decay, step_ptr,
+                              stream);
 }

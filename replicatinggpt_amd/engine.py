@@ -15,6 +15,13 @@ i+1's graph replays on the compute stream meanwhile -- the gradient all-reduce o
 of the backward with only eager collectives (no collective is captured in a graph, so nothing
 here depends on RCCL graph capture).  The optimizer is a final graph replayed after the
 collectives have been waited on.
+
+A learning-rate schedule (``lr_schedule``: iteration -> lr) needs an optimizer in dynamic mode
+(optim.AdamW(dynamic_lr=True) or max_grad_norm): its update reads the learning rate from the device
+when it runs, so ``step`` writes the iteration's value before the replay.  The gradient-norm and
+update kernels of such an optimizer are captured like the default one's: in the step graph on one
+GPU, in the optimizer graph -- replayed after the all-reduce, so the norm is that of the averaged
+gradients -- under data parallelism.
 """
 import torch
 import torch.distributed as dist
@@ -79,8 +86,15 @@ def segment_plan(model, seg_layers):
 
 
 class TrainStep:
-    def __init__(self, model, optimizer, sampler, reducer=None, use_graph=True, overlap=None, seg_layers=2):
+    def __init__(self, model, optimizer, sampler, reducer=None, use_graph=True, overlap=None, seg_layers=2,
+                 lr_schedule=None):
         self.model, self.opt, self.sampler, self.reducer = model, optimizer, sampler, reducer
+        if lr_schedule is not None and not getattr(optimizer, "dynamic_lr", False):
+            raise ValueError("charpt TrainStep: lr_schedule needs an optimizer whose learning rate lives on the device "
+                             "(AdamW(dynamic_lr=True) or max_grad_norm=...): a captured step keeps a by-value "
+                             "learning rate")
+        self.lr_schedule = lr_schedule
+        self.it = 0   # the iteration the next step() takes (settable: a resumed run continues its schedule)
         dev = model.flat.master.device
         B, T = sampler.B, sampler.T
         self.x = torch.empty((B, T), dtype=torch.int64, device=dev)
@@ -192,6 +206,7 @@ class TrainStep:
         gen = self.sampler.generator
         return {"master": st.master.detach().clone(), "m": opt._m.clone(), "v": opt._v.clone(),
                 "step": opt._step_t.clone(), "counter": self.model._rng_counter.clone(),
+                "lr": opt.param_groups[0]["lr"], "it": self.it,
                 "rng": gen.get_state() if gen is not None else torch.get_rng_state()}
 
     def _restore_state(self, s):
@@ -203,6 +218,9 @@ class TrainStep:
             opt._v.copy_(s["v"])
             opt._step_t.copy_(s["step"])
             self.model._rng_counter.copy_(s["counter"])
+        self.it = s["it"]
+        if getattr(opt, "dynamic_lr", False):
+            opt.set_lr(s["lr"])
         st.refresh_shadow()
         gen = self.sampler.generator
         if gen is not None:
@@ -265,6 +283,9 @@ class TrainStep:
     # -- one training step ----------------------------------------------------------------
     def step(self):
         self.sampler.get_batch("train", out=(self.x, self.y))   # GPT1.py:227
+        if self.lr_schedule is not None:
+            self.opt.set_lr(self.lr_schedule(self.it))
+        self.it += 1
         if self.g_seg:
             works = []
             for i, g in enumerate(self.g_seg):

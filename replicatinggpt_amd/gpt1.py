@@ -6,6 +6,8 @@ Hyper-parameters (GPT1.py:8-23), tokenizer and split (:25-70), get_batch (:75-83
 
     python -m replicatinggpt_amd.gpt1                          # as shipped: C1 shape, lr 5e-1
     python -m replicatinggpt_amd.gpt1 --lr 2e-4 --max-iters 500 --dtype bf16
+    python -m replicatinggpt_amd.gpt1 --preset c4 --dtype bf16 --lr 6e-4 --grad-clip 1.0 \
+        --warmup-iters 100 --lr-decay-iters 5000 --min-lr 6e-5   # a recipe GPT1.py does not have
 
 Deliberate differences from GPT1.py:
 
@@ -15,6 +17,10 @@ Deliberate differences from GPT1.py:
 * estimate_loss keeps its per-batch losses on the device and reads them once per split (GPT1.py:94
   synchronises on ``loss.item()`` once per batch); each evaluation forward replays a hipGraph
   (engine.Evaluator).  The mean is taken on the host over the same float32 values, as at :95;
+* ``--grad-clip`` (global-norm clipping) and ``--warmup-iters`` / ``--lr-decay-iters`` / ``--min-lr``
+  (linear warm-up, cosine decay: schedule.warmup_cosine) put the optimizer in its dynamic mode
+  (optim.AdamW); with none of them given the driver builds exactly the objects it built before.  A
+  resumed run continues the schedule from the checkpoint's iteration;
 * dropout masks come from charpt's Philox stream, so with Dropout > 0 the loss
   curve matches the reference's within tolerance, not bit for bit (tests/test_gpu_train.py).
 """
@@ -28,6 +34,7 @@ from .data import DEFAULT_INPUT, BatchSampler, TokenStream
 from .engine import Evaluator, TrainStep
 from .model import BigramLanguageModel
 from .optim import AdamW
+from .schedule import warmup_cosine
 from .sampling import add_sampling_args
 
 
@@ -62,6 +69,10 @@ def parse_args(argv=None):
     ap.add_argument("--eval-iters", type=int)
     ap.add_argument("--dropout", type=float)
     ap.add_argument("--lr", type=float, help="optimizer lr (GPT1.py:218 uses 5e-1; its learning_rate = 2e-4 is unused)")
+    ap.add_argument("--grad-clip", type=float, help="clip the global gradient norm to this (torch clip_grad_norm_)")
+    ap.add_argument("--warmup-iters", type=int, help="linear learning-rate warm-up over this many iterations")
+    ap.add_argument("--lr-decay-iters", type=int, help="cosine decay to --min-lr at this iteration (default: max-iters)")
+    ap.add_argument("--min-lr", type=float, help="the learning rate after the decay (default 0)")
     ap.add_argument("--max-new-tokens", type=int, default=500)
     add_sampling_args(ap)   # --temperature / --top-k / --top-p of the final sample; neutral defaults (GPT1.py:236)
     ap.add_argument("--out", default="model.pth", help="state dict file (GPT1.py:240); '' to skip")
@@ -85,10 +96,26 @@ def main(argv=None):
     cfg = cfg.with_(vocab_size=tok.vocab_size)
     model = BigramLanguageModel(cfg)                                          # GPT1.py:215
     m = model.to(device)                                                      # GPT1.py:216
-    optimizer = AdamW(m.parameters(), lr=a.lr if a.lr is not None else cfg.optimizer_lr)   # GPT1.py:218
+    lr = a.lr if a.lr is not None else cfg.optimizer_lr
+    schedule = None
+    if a.warmup_iters is not None or a.lr_decay_iters is not None or a.min_lr is not None:
+        warm = a.warmup_iters or 0
+        decay = a.lr_decay_iters if a.lr_decay_iters is not None else max(cfg.max_iters, warm)
+        floor = a.min_lr or 0.0
+
+        def schedule(it):
+            return warmup_cosine(it, lr, warm, decay, floor)
+    if schedule is None and a.grad_clip is None:
+        optimizer = AdamW(m.parameters(), lr=lr)                              # GPT1.py:218
+    else:
+        optimizer = AdamW(m.parameters(), lr=lr, max_grad_norm=a.grad_clip, dynamic_lr=True)
     sampler = BatchSampler(stream, cfg.block_size, cfg.batch_size)           # GPT1.py:75-83
     start = checkpoint.load_checkpoint(a.resume, m, optimizer) if a.resume else 0
-    step = TrainStep(m, optimizer, sampler, use_graph=not a.no_graph)
+    if schedule is None:
+        step = TrainStep(m, optimizer, sampler, use_graph=not a.no_graph)
+    else:
+        step = TrainStep(m, optimizer, sampler, use_graph=not a.no_graph, lr_schedule=schedule)
+        step.it = start   # the checkpoint's iteration: the schedule continues where the run stopped
     step.capture(restore=True)
     evaluator = Evaluator(m, sampler, use_graph=not a.no_graph)
     for it in range(start, cfg.max_iters):                                    # GPT1.py:221

@@ -528,6 +528,41 @@ def adamw_segments(p: Tensor, g: Tensor, m: Tensor, v: Tensor, p_bf16: Optional[
                                        beta1, beta2, eps, weight_decay, L.ptr(step), _s(p)), "adamw_segments")
 
 
+@_op("adamw_dyn", ("p", "m", "v", "p_bf16"))
+def adamw_dyn(p: Tensor, g: Tensor, m: Tensor, v: Tensor, p_bf16: Optional[Tensor], lr: Tensor,
+              gscale: Optional[Tensor], beta1: float, beta2: float, eps: float, weight_decay: float,
+              step: Tensor) -> None:
+    """adamw with the learning rate a device float64 scalar read when the kernel runs and, when given,
+    the gradient multiplied by the device float32 scalar ``gscale`` first (g itself stays as it is)."""
+    if lr.dtype != torch.float64 or (gscale is not None and gscale.dtype != torch.float32):
+        raise TypeError("charpt adamw_dyn: lr must be a float64 tensor, gscale a float32 tensor")
+    L.check(L.load().cg_adamw_dyn(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(p_bf16), p.numel(), L.ptr(lr),
+                                  L.ptr(gscale), beta1, beta2, eps, weight_decay, L.ptr(step), _s(p)), "adamw_dyn")
+
+
+def grad_norm_workspace(n: int) -> int:
+    return int(L.load().cg_grad_norm_workspace(n))
+
+
+@_op("grad_norm", ("out", "ws"))
+def grad_norm(g: Tensor, max_norm: float, out: Tensor, ws: Tensor) -> None:
+    """out[0] = the L2 norm of g (fp64 accumulation, deterministic), out[1] = min(1, max_norm / (norm + 1e-6));
+    out: 2 float32, ws: grad_norm_workspace(g.numel()) bytes."""
+    if not g.is_contiguous() or g.dtype != torch.float32 or out.dtype != torch.float32 or out.numel() < 2:
+        raise ValueError("charpt grad_norm: g must be contiguous float32, out two float32")
+    if ws.numel() * ws.element_size() < grad_norm_workspace(g.numel()):
+        raise ValueError("charpt grad_norm: workspace too small")
+    L.check(L.load().cg_grad_norm(L.ptr(g), g.numel(), max_norm, L.ptr(out), L.ptr(ws), _s(g)), "grad_norm")
+
+
+@_op("scale_", ("x",))
+def scale_(x: Tensor, scale: Tensor) -> None:
+    """x *= scale (a device float32 scalar), in place."""
+    if not x.is_contiguous() or x.dtype != torch.float32 or scale.dtype != torch.float32:
+        raise ValueError("charpt scale_: x must be contiguous float32, scale a float32 tensor")
+    L.check(L.load().cg_scale_f32(L.ptr(x), x.numel(), L.ptr(scale), _s(x)), "scale_f32")
+
+
 # ---------------------------------------------------------------------------------------
 # Fake (meta) implementations of the out-style ops above: each returns None and only writes
 # buffers it declares as mutated, so FakeTensor / torch.compile tracing treats it as a no-op on

@@ -4,6 +4,12 @@ One kernel launch updates every parameter, its two moments and the bf16 weight s
 GEMMs read.  The step count lives on the device, so the whole optimizer step is capturable in a
 hipGraph.  Numerics follow torch/optim/adam.py ``_single_tensor_adam`` (decoupled weight decay,
 bias-corrected moments, same fp32 operation order).
+
+Dynamic mode (``dynamic_lr=True`` or ``max_grad_norm`` set) keeps the learning rate in a device
+float64 that the kernel reads when it runs (cg_adamw_dyn), so a captured step follows a schedule
+(``set_lr``), and clips by the global gradient norm on the device: cg_grad_norm over the flat
+gradient buffer, its coefficient multiplied in by the update itself.  ``p.grad`` is left UNSCALED
+by the optimizer's clipping (torch's clip_grad_norm_ scales it; ``clip_grad_norm_`` below does too).
 """
 import torch
 
@@ -12,7 +18,10 @@ from . import ops
 
 
 class AdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
+                 dynamic_lr=False):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"charpt AdamW: max_grad_norm must be > 0 (got {max_grad_norm})")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._store = None
@@ -21,6 +30,13 @@ class AdamW(torch.optim.Optimizer):
         self._psteps = None   # per-parameter step counts, once a step skipped some parameter
         self._early = None    # flat (offset, n) ranges updated early this step (functional.EARLY)
         self._poisoned = None  # why the state is half a step ahead (a failed backward after early updates ran)
+        # constructor settings, not checkpoint state: state_dict() stays torch's
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.dynamic_lr = bool(dynamic_lr) or max_grad_norm is not None
+        self._lr_t = None        # dynamic mode: the learning rate, a device float64
+        self._lr_written = None  # the value last written to it
+        self._clip = None        # clipping: [gradient norm, clip coefficient], device float32
+        self._norm_ws = None     # cg_grad_norm's block partials
 
     # the model whose flat store holds these parameters is found from the parameters, so
     # ``AdamW(m.parameters(), lr=5e-1)`` works exactly as GPT1.py:218 writes it
@@ -46,6 +62,12 @@ class AdamW(torch.optim.Optimizer):
         self._v = torch.zeros_like(st.master)
         self._step_t = torch.zeros(1, dtype=torch.int64, device=st.master.device)
         self._psteps = None
+        if self.dynamic_lr:
+            dev = st.master.device
+            self._lr_written = float(self.param_groups[0]["lr"])
+            self._lr_t = torch.full((1,), self._lr_written, dtype=torch.float64, device=dev)
+        if self.max_grad_norm is not None:
+            self._clip = torch.tensor([0.0, 1.0], dtype=torch.float32, device=st.master.device)
         return self
 
     def _ensure(self):
@@ -58,6 +80,34 @@ class AdamW(torch.optim.Optimizer):
             self._step_t = self._step_t.to(st.master.device)
             if self._psteps is not None:
                 self._psteps = self._psteps.to(st.master.device)
+            if self._lr_t is not None:
+                self._lr_t = self._lr_t.to(st.master.device)
+            if self._clip is not None:
+                self._clip = self._clip.to(st.master.device)
+            self._norm_ws = None
+
+    # -- dynamic mode: device learning rate, global-norm clipping ---------------------------------
+    def set_lr(self, lr):
+        """The learning rate of the next step: ``param_groups[0]["lr"]`` and the device scalar the
+        kernel reads (a captured step replays with it).  Dynamic mode only."""
+        if not self.dynamic_lr:
+            raise RuntimeError("charpt AdamW: set_lr needs dynamic_lr=True (or max_grad_norm): the default path passes "
+                               "the learning rate by value, and a captured step keeps the value it was captured with")
+        self._ensure()
+        self.param_groups[0]["lr"] = lr
+        self._lr_written = float(lr)
+        self._lr_t.fill_(self._lr_written)
+
+    @property
+    def grad_norm(self):
+        """The last step's global gradient norm before clipping: a device scalar (no sync), valid
+        until the next step.  Needs max_grad_norm."""
+        return None if self._clip is None else self._clip[0]
+
+    @property
+    def clip_coef(self):
+        """The last step's clip coefficient min(1, max_grad_norm / (norm + 1e-6)), likewise."""
+        return None if self._clip is None else self._clip[1]
 
     # -- early updates (functional.EarlyAdam, engine.TrainStep) -----------------------------------
     def _args(self):
@@ -66,9 +116,12 @@ class AdamW(torch.optim.Optimizer):
         return (float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]))
 
     def early_ok(self):
-        """One step count for every parameter, all of them trained, flat buffers on the GPU."""
+        """One step count for every parameter, all of them trained, flat buffers on the GPU.  Never in
+        dynamic mode: with clipping no update may run before the global norm exists, and the
+        GEMM-hosted updates take the learning rate by value (a device-lr field for them is left to a
+        follow-up)."""
         self._ensure()
-        return (self._psteps is None and self._store.master.is_cuda and
+        return (not self.dynamic_lr and self._psteps is None and self._store.master.is_cuda and
                 all(p.requires_grad for g in self.param_groups for p in g["params"]))
 
     def _check_poisoned(self):
@@ -147,6 +200,10 @@ class AdamW(torch.optim.Optimizer):
                 slot = r.slot.view(-1)[off:off + p.numel()].view(p.shape)
                 if p.grad.data_ptr() != slot.data_ptr():
                     slot.copy_(p.grad)
+        if self.dynamic_lr:
+            self._step_dynamic(missing)
+            st._shadow_version = st.version()
+            return loss
         args = (float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]))
         if self._early is not None:
             # the step count was advanced when the backward began and the weight matrices were
@@ -183,6 +240,43 @@ class AdamW(torch.optim.Optimizer):
                           st.shadow[off:off + n], *args, step)
         st._shadow_version = st.version()
         return loss
+
+    def _step_dynamic(self, missing):
+        """The step in dynamic mode: [cg_grad_norm over the whole flat gradient buffer -- its alignment
+        padding and the lm_head pad rows are zero, as the one-launch update already relies on --] and
+        cg_adamw_dyn, which reads the learning rate and the clip coefficient from the device."""
+        st = self._store
+        grp = self.param_groups[0]
+        if float(grp["lr"]) != self._lr_written:   # a torch scheduler or a plain assignment (eager steps)
+            self.set_lr(grp["lr"])
+        b1, b2 = grp["betas"]
+        hyper = (float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]))
+        coef = None
+        if self.max_grad_norm is not None:
+            if missing:
+                raise RuntimeError(f"charpt AdamW: max_grad_norm is set and {len(missing)} parameter(s) have no "
+                                   ".grad: the global norm is taken over the flat gradient buffer, which would "
+                                   "still hold their last gradients")
+            if self._norm_ws is None:
+                self._norm_ws = torch.empty(ops.grad_norm_workspace(st.numel) // 8, dtype=torch.float64,
+                                            device=st.master.device)
+            ops.grad_norm(st.grad, self.max_grad_norm, self._clip, self._norm_ws)
+            coef = self._clip[1:2]
+        if not missing and self._psteps is None:
+            ops.counter_add(self._step_t, 1)
+            ops.adamw_dyn(st.master, st.grad, self._m, self._v, st.shadow, self._lr_t, coef, *hyper, self._step_t)
+            return
+        # parameters without a gradient are skipped as torch skips them: per-parameter launches and counts
+        self._split_steps()
+        skip = {id(p) for p in missing}
+        for i, p, off in self._param_slices():
+            if id(p) in skip:
+                continue
+            n = p.numel()
+            step = self._psteps[i:i + 1]
+            ops.counter_add(step, 1)
+            ops.adamw_dyn(st.master[off:off + n], st.grad[off:off + n], self._m[off:off + n], self._v[off:off + n],
+                          st.shadow[off:off + n], self._lr_t, coef, *hyper, step)
 
     def _early_step_with_missing(self, early, missing, args):
         """A step with early updates in which some parameters had no gradient (torch.optim.AdamW
@@ -272,3 +366,30 @@ class AdamW(torch.optim.Optimizer):
             self._step_t.fill_(steps[0] if steps else 0)
         else:   # parameters that skipped steps (grad None) resume with their own counts
             self._psteps = torch.tensor(steps, dtype=torch.int64, device=self._step_t.device)
+        if self.dynamic_lr:
+            self.set_lr(grp["lr"])
+
+
+def clip_grad_norm_(model, max_norm):
+    """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) for hand-written GPT1.py-style
+    loops, on the device: the global L2 norm of the model's flat gradient buffer (cg_grad_norm,
+    deterministic) and the in-place scale by min(1, max_norm / (norm + 1e-6)) (cg_scale_f32) -- every
+    ``p.grad`` is a view of that buffer, so it is scaled as torch scales it.  Returns the norm before
+    clipping as a device scalar (no sync).  Every parameter's gradient must sit in its flat slot, as
+    the backward leaves it."""
+    if not float(max_norm) > 0:
+        raise ValueError(f"charpt clip_grad_norm_: max_norm must be > 0 (got {max_norm})")
+    st = model.flat
+    Fn.SIDE.join()   # weight gradients computed on the side stream must be final
+    for r in st.regions.values():
+        for p, off in r.parts:
+            slot = r.slot.view(-1)[off:off + p.numel()]
+            if p.grad is None or p.grad.data_ptr() != slot.data_ptr():
+                raise RuntimeError("charpt clip_grad_norm_: a parameter's gradient is missing from its slot in the "
+                                   "flat gradient buffer (.grad is None, or was assigned from outside)")
+    dev = st.grad.device
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = torch.empty(ops.grad_norm_workspace(st.numel) // 8, dtype=torch.float64, device=dev)
+    ops.grad_norm(st.grad, float(max_norm), out, ws)
+    ops.scale_(st.grad, out[1:2])
+    return out[0]
