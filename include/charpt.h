@@ -388,6 +388,36 @@ int cg_decode_sample(const float* logits, int64_t ldl, int64_t V, int64_t B, int
 int cg_decode_sample_filtered(const float* logits, int64_t ldl, int64_t V, int64_t B, const float* params_dev,
                               const uint64_t* seed_dev, const int64_t* len_dev, int64_t* idx, int64_t ld,
                               void* stream);
+/* The per-row epilogue of a ragged batch (BigramLanguageModel.complete): the two samplers above plus
+   forced prompt tokens, stop tokens, a per-row budget and per-token log-probabilities, one launch per
+   decode step, one row per workgroup.  All rows share n = *len_dev; every argument below except
+   mode, the sizes and the strides is device memory read when the kernel runs, so a captured graph
+   serves every prompt set, stop set, pad token and sampling setting.
+     mode          0: greedy, 1: plain draw (cg_decode_sample greedy = 1 / 0), 2: filtered draw
+                   (cg_decode_sample_filtered with params_dev = {tau, k, p}; NULL allowed otherwise);
+     prompt_len[B] int64: the row's prompt length;
+     limit[B]      int64: the length at which the row ends (prompt_len + max_new_tokens);
+     end[B]        int64, read and written: 0 = the row is running, else its final length;
+     stop_bits     ceil(V / 64) uint64 words: bit v (word v / 64, bit v % 64) set = token v ends a row;
+     pad_dev       one int64: the token written into ended rows;
+     idx[B, ld], logprob[B, ld] (fp32; NULL: no log-probabilities): one row stride for both.
+   Per row b:
+     1. end[b] != 0 (ended): idx[b, n] <- *pad_dev and logprob[b, n] <- 0; nothing else is written.
+     2. n < prompt_len[b] (forced): the token is idx[b, n]; idx is not written.
+     3. otherwise (emitted): the token is exactly what cg_decode_sample (modes 0, 1) or
+        cg_decode_sample_filtered (mode 2) writes for these logits, *seed_dev, len = n and row b --
+        their NaN and +inf rules included (the kernels share the choice code); idx[b, n] <- token.
+     4. logprob given: logprob[b, n] <- (x[tok] - m) - log(sum_v exp(x[v] - m)) over the raw fp32
+        logits x (temperature 1, no cuts; m = max x; fp32 accumulation), for forced tokens too; NaN
+        when the row holds NaN or +inf, or a forced token lies outside [0, V).
+     5. an emitted (not forced) token whose stop bit is set: end[b] <- n + 1; otherwise n + 1 ==
+        limit[b]: end[b] <- n + 1.
+   Plain stores only; the host polls end[] outside the graph.  The caller keeps n < ld and then
+   advances *len_dev.  1 <= V <= 1024, ldl >= V and mode in {0, 1, 2}, else CG_EINVAL.             */
+int cg_decode_emit(const float* logits, int64_t ldl, int64_t V, int64_t B, int mode, const float* params_dev,
+                   const uint64_t* seed_dev, const int64_t* len_dev, const int64_t* prompt_len, const int64_t* limit,
+                   int64_t* end, const uint64_t* stop_bits, const int64_t* pad_dev, int64_t* idx, int64_t ld,
+                   float* logprob, void* stream);
 
 /* ---- fused AdamW over a flat fp32 buffer (torch.optim.AdamW, GPT1.py:218,233) ------------
    step_ptr: device int64 step count (already incremented for this step).

@@ -9,7 +9,8 @@
 //            through ln_f / lm_head;
 // and samples on the device (cg_decode_sample: argmax, or inverse-CDF sampling from a Philox
 // stream; cg_decode_sample_filtered: that draw under a temperature, a top-k and a top-p cut read
-// from device memory).  Every step's shapes are static and the current length lives in device
+// from device memory; cg_decode_emit: either, as the per-row epilogue of a ragged batch -- forced
+// prompt tokens, stop tokens, per-row limits, log-probabilities).  Every step's shapes are static and the current length lives in device
 // memory, so each phase is captured once as a hipGraph and replayed per token.
 #include "common.h"
 
@@ -273,17 +274,13 @@ __device__ __forceinline__ bool argmax_ahead(float x, int v, float best, int bi)
     return best == best && (x > best || (x == best && v < bi));
 }
 
-// next token per row from logits [B, V]: greedy = first argmax (torch.argmax tie and NaN rule); else
-// inverse-CDF sampling of softmax(logits) with u = Philox(seed, stream = step)[b] / 2^32.
-// Writes idx[b, len] (len = *len_dev) -- the caller then advances *len_dev.
-__global__ __launch_bounds__(64) void k_decode_sample(const float* __restrict__ logits, int64_t ldl, int64_t V,
-                                                      int64_t B, int greedy, const uint64_t* __restrict__ seed_dev,
-                                                      const int64_t* __restrict__ len_dev,
-                                                      int64_t* __restrict__ idx, int64_t ld) {
-    const int64_t b = blockIdx.x;
-    if (b >= B) return;
-    const int lane = threadIdx.x;
-    const float* row = logits + b * ldl;
+// The token k_decode_sample writes for one row, computed by one wave (lane = 0..63, every lane active);
+// the return value is the token in lane 0 (cg_decode_emit's modes 0 and 1 call this too, so the two
+// kernels agree by construction): greedy = first argmax (torch.argmax tie and NaN rule); else
+// inverse-CDF sampling of softmax(row) with u = Philox(seed, stream = len)[b] / 2^32.
+__device__ __forceinline__ int64_t choose_plain(const float* __restrict__ row, int64_t V, int greedy,
+                                                const uint64_t* __restrict__ seed_dev, int64_t len, int64_t b,
+                                                int lane) {
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int v = lane; v < V; v += 64) {
@@ -296,7 +293,6 @@ __global__ __launch_bounds__(64) void k_decode_sample(const float* __restrict__ 
         const int oi = __shfl_xor(bi, off, 64);
         if (argmax_ahead(ob, oi, best, bi)) { best = ob; bi = oi; }
     }
-    const int64_t len = *len_dev;
     int64_t tok = bi;
     if (!greedy) {
         float s = 0.f;
@@ -314,6 +310,20 @@ __global__ __launch_bounds__(64) void k_decode_sample(const float* __restrict__ 
             }
         }
     }
+    return tok;
+}
+
+// next token per row from logits [B, V] (choose_plain).
+// Writes idx[b, len] (len = *len_dev) -- the caller then advances *len_dev.
+__global__ __launch_bounds__(64) void k_decode_sample(const float* __restrict__ logits, int64_t ldl, int64_t V,
+                                                      int64_t B, int greedy, const uint64_t* __restrict__ seed_dev,
+                                                      const int64_t* __restrict__ len_dev,
+                                                      int64_t* __restrict__ idx, int64_t ld) {
+    const int64_t b = blockIdx.x;
+    if (b >= B) return;
+    const int lane = threadIdx.x;
+    const int64_t len = *len_dev;
+    const int64_t tok = choose_plain(logits + b * ldl, V, greedy, seed_dev, len, b, lane);
     if (lane == 0) idx[b * ld + len] = tok;
 }
 
@@ -333,28 +343,23 @@ __global__ __launch_bounds__(64) void k_decode_sample(const float* __restrict__ 
 // be the first column past the draw: with everything kept and tau = 1 (x / 1.0f is exact) the token
 // is k_decode_sample's bit for bit.
 constexpr int SAMPLE_VMAX = 1024;
-__global__ __launch_bounds__(256) void k_decode_sample_filtered(const float* __restrict__ logits, int64_t ldl,
-                                                                int V, int64_t B,
-                                                                const float* __restrict__ params,
-                                                                const uint64_t* __restrict__ seed_dev,
-                                                                const int64_t* __restrict__ len_dev,
-                                                                int64_t* __restrict__ idx, int64_t ld) {
+// choose_filtered: the token for row b, valid in thread 0 (what other threads return is unspecified);
+// every thread of the 256-thread block must call it (it holds block barriers).  k_decode_sample_filtered
+// and cg_decode_emit's mode 2 both call it.
+__device__ __forceinline__ int choose_filtered(const float* __restrict__ row, int V, const float* __restrict__ params,
+                                               uint64_t seed, int64_t len, int64_t b) {
     constexpr int NT = 256, J = SAMPLE_VMAX / NT;
     __shared__ float4 xs4[SAMPLE_VMAX / 4], wv4[SAMPLE_VMAX / 4];
     __shared__ float ws[SAMPLE_VMAX];
     __shared__ int sh_keep, sh_last;
     float* xs = (float*)xs4;
     float* wv = (float*)wv4;
-    const int64_t b = blockIdx.x;
-    if (b >= B) return;
     const int tid = threadIdx.x, lane = tid & 63;
-    const float* row = logits + b * ldl;
     const int Vp = (V + 3) & ~3;
     const int nj = (V + NT - 1) / NT;   // column passes in use (1 up to V = 256)
-    // every scalar the kernel needs, loaded beside the row (not one global round trip after another)
+    // every scalar the kernel needs is loaded beside the row (not one global round trip after another):
+    // the caller reads len and the seed before the call
     const float tau = params[0], kf = params[1], p = params[2];
-    const int64_t len = *len_dev;
-    const uint64_t seed = seed_dev ? *seed_dev : 0ull;
     for (int v = tid; v < Vp; v += NT) xs[v] = v < V ? row[v] : -INFINITY;
     if (tid == 0) sh_last = -1;
     __syncthreads();
@@ -371,10 +376,7 @@ __global__ __launch_bounds__(256) void k_decode_sample_filtered(const float* __r
         const int oi = __shfl_xor(bi, off, 64);
         if (argmax_ahead(ob, oi, best, bi)) { best = ob; bi = oi; }
     }
-    if (best != best || best == INFINITY) {   // a NaN or +inf in the row: the greedy rule's token
-        if (tid == 0) idx[b * ld + len] = bi;
-        return;
-    }
+    if (best != best || best == INFINITY) return bi;   // a NaN or +inf in the row: the greedy rule's token
     const int kk = kf >= 1.f && kf < (float)V ? (int)kf : V;   // 0, k >= V (and NaN): top-k off
     const bool nucleus = p < 1.f;                                // p >= 1 (and NaN): top-p off
     const bool filtered = kk < V || nucleus;
@@ -457,15 +459,16 @@ __global__ __launch_bounds__(256) void k_decode_sample_filtered(const float* __r
         if (last >= 0) atomicMax(&sh_last, last);
     }
     __syncthreads();
-    if (tid >= 64) return;
+    if (tid >= 64) return 0;
     // the draw: k_decode_sample's sum pattern and sequential scan over the kept weights
     float s = 0.f;
     for (int v = lane; v < V; v += 64) s += wv[v];
     s = wave_sum(s);
     const u32x4 r = philox_group(seed, (uint64_t)len, (uint64_t)b);
     const float u = (float)(r.x >> 8) * (1.0f / 16777216.0f) * s;  // 24-bit uniform in [0, s)
+    int tok = 0;
     if (lane == 0) {
-        int tok = filtered ? sh_last : V - 1;   // no column past the draw: the last kept one
+        tok = filtered ? sh_last : V - 1;   // no column past the draw: the last kept one
         float c = 0.f;
         bool found = false;
         float4 next = wv4[0];
@@ -479,8 +482,84 @@ __global__ __launch_bounds__(256) void k_decode_sample_filtered(const float* __r
                 if (!found && u < c) { tok = v + e; found = true; }
             }
         }
-        idx[b * ld + len] = tok;
     }
+    return tok;
+}
+
+__global__ __launch_bounds__(256) void k_decode_sample_filtered(const float* __restrict__ logits, int64_t ldl,
+                                                                int V, int64_t B,
+                                                                const float* __restrict__ params,
+                                                                const uint64_t* __restrict__ seed_dev,
+                                                                const int64_t* __restrict__ len_dev,
+                                                                int64_t* __restrict__ idx, int64_t ld) {
+    const int64_t b = blockIdx.x;
+    if (b >= B) return;
+    const int64_t len = *len_dev;
+    const uint64_t seed = seed_dev ? *seed_dev : 0ull;
+    const int tok = choose_filtered(logits + b * ldl, V, params, seed, len, b);
+    if (threadIdx.x == 0) idx[b * ld + len] = tok;
+}
+
+// log softmax(row)[tok] over the raw logits (temperature 1, no cuts), by one wave: (x[tok] - m) - log of
+// the sum of exp(x[v] - m), m the row maximum, fp32 (lane-strided partial sums, then wave_sum).  NaN for a
+// row holding NaN or +inf, and for a tok outside [0, V) (a caller's prompt token: nothing is read there).
+__device__ __forceinline__ float row_logprob(const float* __restrict__ row, int V, int64_t tok, int lane) {
+    float m = -INFINITY;
+    bool bad = false;
+    for (int v = lane; v < V; v += 64) {
+        const float x = row[v];
+        bad |= x != x || x == INFINITY;
+        m = fmaxf(m, x);
+    }
+    m = wave_max(m);
+    float s = 0.f;
+    for (int v = lane; v < V; v += 64) s += __expf(row[v] - m);
+    s = wave_sum(s);
+    if (__ballot(bad) || tok < 0 || tok >= V) return __builtin_nanf("");
+    return (row[tok] - m) - logf(s);
+}
+
+// The ragged engine's per-row epilogue (include/charpt.h cg_decode_emit): one block per row, 64 threads
+// (modes 0 and 1: choose_plain) or 256 (mode 2: choose_filtered), so an emitted token is the old
+// samplers' by construction.  Every branch below is block-uniform; thread 0 does all the stores.
+template <bool FILTERED>
+__global__ __launch_bounds__(FILTERED ? 256 : 64) void k_decode_emit(
+    const float* __restrict__ logits, int64_t ldl, int V, int64_t B, int greedy, const float* __restrict__ params,
+    const uint64_t* __restrict__ seed_dev, const int64_t* __restrict__ len_dev,
+    const int64_t* __restrict__ prompt_len, const int64_t* __restrict__ limit, int64_t* __restrict__ end,
+    const uint64_t* __restrict__ stop_bits, const int64_t* __restrict__ pad_dev, int64_t* __restrict__ idx,
+    int64_t ld, float* __restrict__ logprob) {
+    const int64_t b = blockIdx.x;
+    if (b >= B) return;
+    const int tid = threadIdx.x;
+    const int64_t n = *len_dev;
+    const uint64_t seed = seed_dev ? *seed_dev : 0ull;
+    const int64_t plen = prompt_len[b], lim = limit[b], ended = end[b];
+    if (ended != 0) {   // an ended row: pad, log-prob 0
+        if (tid == 0) {
+            idx[b * ld + n] = *pad_dev;
+            if (logprob) logprob[b * ld + n] = 0.f;
+        }
+        return;
+    }
+    const float* row = logits + b * ldl;
+    const bool forced = n < plen;
+    int64_t tok;
+    if (forced) {
+        tok = idx[b * ld + n];
+    } else {
+        if constexpr (FILTERED) tok = choose_filtered(row, V, params, seed, n, b);
+        else tok = choose_plain(row, V, greedy, seed_dev, n, b, tid);
+    }
+    if (tid >= 64) return;
+    if (!forced) tok = __shfl((int)tok, 0, 64);   // thread 0 holds it
+    float lp = 0.f;
+    if (logprob) lp = row_logprob(row, V, tok, tid);
+    if (tid != 0) return;
+    if (!forced) idx[b * ld + n] = tok;
+    if (logprob) logprob[b * ld + n] = lp;
+    if (!forced && ((stop_bits[tok >> 6] >> (tok & 63)) & 1ull)) end[b] = n + 1;
+    else if (n + 1 == lim) end[b] = n + 1;
 }
 
 }  // namespace
@@ -555,5 +634,29 @@ extern "C" int cg_decode_sample_filtered(const float* logits, int64_t ldl, int64
     k_decode_sample_filtered<<<(unsigned)B, 256, 0, (hipStream_t)stream>>>(logits, ldl, (int)V, B, params_dev,
                                                                            seed_dev, len_dev, idx, ld);
     CG_LAUNCH_CHECK("cg_decode_sample_filtered");
+    return CG_OK;
+}
+
+extern "C" int cg_decode_emit(const float* logits, int64_t ldl, int64_t V, int64_t B, int mode, const float* params_dev,
+                              const uint64_t* seed_dev, const int64_t* len_dev, const int64_t* prompt_len,
+                              const int64_t* limit, int64_t* end, const uint64_t* stop_bits, const int64_t* pad_dev,
+                              int64_t* idx, int64_t ld, float* logprob, void* stream) {
+    CG_REQUIRE(B > 0 && ld > 0, "cg_decode_emit: bad sizes (B = %lld, ld = %lld)", (long long)B, (long long)ld);
+    CG_REQUIRE(V >= 1 && V <= SAMPLE_VMAX, "cg_decode_emit: V = %lld is outside the kernel's range 1..%d", (long long)V,
+               SAMPLE_VMAX);
+    CG_REQUIRE(ldl >= V, "cg_decode_emit: ldl = %lld is below V = %lld", (long long)ldl, (long long)V);
+    CG_REQUIRE(mode >= 0 && mode <= 2, "cg_decode_emit: mode = %d is not 0 (greedy), 1 (draw) or 2 (filtered draw)", mode);
+    CG_REQUIRE(logits && len_dev && prompt_len && limit && end && stop_bits && pad_dev && idx,
+               "cg_decode_emit: null pointer");
+    CG_REQUIRE(mode != 2 || params_dev, "cg_decode_emit: mode 2 needs params_dev");
+    if (mode == 2)
+        k_decode_emit<true><<<(unsigned)B, 256, 0, (hipStream_t)stream>>>(logits, ldl, (int)V, B, 0, params_dev, seed_dev,
+                                                                           len_dev, prompt_len, limit, end, stop_bits,
+                                                                           pad_dev, idx, ld, logprob);
+    else
+        k_decode_emit<false><<<(unsigned)B, 64, 0, (hipStream_t)stream>>>(logits, ldl, (int)V, B, mode == 0, params_dev,
+                                                                           seed_dev, len_dev, prompt_len, limit, end,
+                                                                           stop_bits, pad_dev, idx, ld, logprob);
+    CG_LAUNCH_CHECK("cg_decode_emit");
     return CG_OK;
 }

@@ -22,7 +22,13 @@ computed as:
   nucleus cuts keep, weights at the temperature.  The three settings live in a device buffer the
   kernel reads when it runs, so ``generate(..., sampling=(t, k, p))`` rewrites twelve bytes and
   replays the graphs captured once; neutral settings there give ``cg_decode_sample``'s tokens
-  bit for bit.
+  bit for bit;
+* a ragged engine (``ragged=True``: ``BigramLanguageModel.complete`` / ``score``) runs prompts of
+  different lengths in lock step through the same two steps with ``cg_decode_emit`` as the sampling
+  launch: it leaves ``idx[b, len]`` alone while ``len < prompt_len[b]`` (a forced token), writes the
+  samplers' token after that, ends a row at a stop token or at its limit, pads ended rows and, on
+  request, stores every token's log-probability.  Prompt lengths, limits, end flags, the stop set,
+  the pad token and the sampling settings are device buffers rewritten per call.
 
 The current length lives in a device int64, so each phase's step is one static-shape hipGraph
 captured once and replayed per token (prefill of a longer prompt replays the phase-1 graph without
@@ -40,13 +46,17 @@ from .sampling import check_sampling, sampling_params
 DECODE_ROWS = os.environ.get("CHARPT_DECODE_ROWS", "1") == "1"
 # CHARPT_LAST_KV_SPLIT=0: the window step's last block computes Q for every row too (A/B)
 LAST_KV_SPLIT = os.environ.get("CHARPT_LAST_KV_SPLIT", "1") == "1"
+EMIT_GREEDY, EMIT_DRAW, EMIT_FILTERED = 0, 1, 2   # cg_decode_emit's mode
 
 
 class DecodeEngine:
-    def __init__(self, model, batch, max_len, greedy=True, seed=0, use_graph=True, filtered=False):
+    def __init__(self, model, batch, max_len, greedy=True, seed=0, use_graph=True, filtered=False, ragged=False,
+                 logprobs=False):
         cfg = model.config
-        if filtered and greedy:
+        if filtered and greedy and not ragged:
             raise ValueError("DecodeEngine: filtered sampling and greedy exclude each other")
+        if logprobs and not ragged:
+            raise ValueError("DecodeEngine: logprobs=True needs ragged=True")
         self.m, self.B, self.max_len = model, int(batch), int(max_len)
         self.T, self.C, self.H = cfg.block_size, cfg.n_embd, cfg.n_head
         self.D = self.C // self.H
@@ -70,6 +80,18 @@ class DecodeEngine:
         self.logits = torch.empty((B, self.V), dtype=torch.float32, device=dev)
         self.use_graph = use_graph and dev.type == "cuda"
         self.g1 = self.g1_prefill = self.g2 = None
+        self.ragged = bool(ragged)
+        if self.ragged:
+            # everything complete() varies per call is device memory cg_decode_emit reads when it runs
+            self.params = sampling_params().to(dev)
+            self.mode = EMIT_GREEDY            # a launch argument: one (g1, g2) pair per mode used
+            self.prompt_len = torch.zeros(B, dtype=torch.int64, device=dev)
+            self.limit = torch.zeros(B, dtype=torch.int64, device=dev)
+            self.end = torch.zeros(B, dtype=torch.int64, device=dev)
+            self.stop_bits = torch.zeros((self.V + 63) // 64, dtype=torch.int64, device=dev)
+            self.pad = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.logprob = torch.zeros((B, self.max_len), dtype=torch.float32, device=dev) if logprobs else None
+            self.rg = {}                       # mode -> (g1, g2)
 
     # -- regions -------------------------------------------------------------------------
     def _R(self, key):
@@ -115,7 +137,10 @@ class DecodeEngine:
         self._ln_linear(x2, "lnf", self._R("lm_w").operand(self.act), self.logits, bias=self._b("lm_b"))
 
     def _sample(self):
-        if self.filtered:
+        if self.ragged:
+            ops.decode_emit(self.logits, self.mode, self.params, self.seed, self.len, self.prompt_len, self.limit,
+                            self.end, self.stop_bits, self.pad, self.idx, self.logprob)
+        elif self.filtered:
             ops.decode_sample_filtered(self.logits, self.params, self.seed, self.len, self.idx)
         else:
             ops.decode_sample(self.logits, self.greedy, self.seed, self.len, self.idx)
@@ -214,6 +239,8 @@ class DecodeEngine:
     def generate(self, idx, max_new_tokens, seed=None, sampling=None):
         """``sampling``: (temperature, top_k, top_p) for a filtered engine -- written to the device
         buffer the sampler reads, so every setting replays the same graphs; None keeps the last."""
+        if self.ragged:
+            raise ValueError("DecodeEngine: a ragged engine runs complete(), not generate()")
         B, L0 = idx.shape
         if sampling is not None:
             if not self.filtered:
@@ -258,5 +285,103 @@ class DecodeEngine:
                     self.g2.replay() if self.g2 else self._step2()
                 n += 1
             return self.idx[:, :total].clone()
+        finally:
+            self.m.train(was_training)
+
+    # -- ragged batches (BigramLanguageModel.complete) ---------------------------------------------
+    def _ragged_graphs(self):
+        """(g1, g1_prefill, g2) for the current mode, captured on first use (None each without graphs).
+        The prefill step launches no emit kernel, so one graph serves every mode."""
+        if not self.use_graph:
+            return None, None, None
+        if self.mode not in self.rg:
+            # the warm-up runs scribble on idx / caches / end / logprob: complete() writes them afterwards
+            self.len.fill_(1)
+            if self.g1_prefill is None:
+                self.g1_prefill = self._graph(lambda: self._step1(False))
+            g1 = self._graph(lambda: self._step1(True))
+            g2 = self._graph(self._step2) if self.max_len > self.T else None
+            self.rg[self.mode] = (g1, g2)
+        g1, g2 = self.rg[self.mode]
+        return g1, self.g1_prefill, g2
+
+    @torch.no_grad()
+    def complete(self, idx, lens, max_new_tokens, mode=EMIT_GREEDY, seed=None, sampling=None, stop_bits=None, pad=0,
+                 poll_every=32):
+        """Continue a ragged batch in lock step: row b's prompt is idx[b, :lens[b]] (lens a CPU int64
+        tensor, every entry in [1, idx.shape[1]]), and it runs until a stop token or lens[b] +
+        max_new_tokens.  Column n of every row is decided by one cg_decode_emit launch after the step
+        that consumed column n - 1: forced while n < lens[b], the sampler's token after that, pad once
+        the row has ended -- so the phase-1 and phase-2 steps above run unchanged.  stop_bits: a CPU
+        int64 tensor of ceil(V / 64) words (None: no stop token).  Returns (tokens [B, max(lens) +
+        max_new_tokens], lengths [B], logprobs or None, head steps run)."""
+        if not self.ragged:
+            raise ValueError("DecodeEngine: complete() needs an engine built with ragged=True")
+        B, Lmax = idx.shape
+        pmin, pmax = int(lens.min()), int(lens.max())
+        total = pmax + max_new_tokens
+        if B != self.B or lens.numel() != B or pmin < 1 or pmax > Lmax or max_new_tokens < 0 or total > self.max_len:
+            raise ValueError(f"DecodeEngine(batch={self.B}, max_len={self.max_len}) cannot run prompts of lengths "
+                             f"{lens.tolist()} in idx {tuple(idx.shape)} + {max_new_tokens} tokens")
+        if mode not in (EMIT_GREEDY, EMIT_DRAW, EMIT_FILTERED):
+            raise ValueError(f"DecodeEngine: mode must be 0 (greedy), 1 (draw) or 2 (filtered draw), got {mode!r}")
+        if sampling is not None:
+            check_sampling(*sampling)
+        want_lp = self.logprob is not None
+        # the first column an emit launch has to decide: with log-probs every column from 1, else the
+        # first one past the shortest prompt
+        n0 = 1 if want_lp else (pmin if max_new_tokens > 0 else total)
+        was_training = self.m.training
+        self.m.eval()
+        try:
+            if self.act == torch.bfloat16:
+                self.m._sync_shadow()
+            self.mode = int(mode)
+            g1, g1p, g2 = self._ragged_graphs() if n0 < total else (None, None, None)
+            if sampling is not None:
+                self.params.copy_(sampling_params(*sampling))
+            if seed is not None:
+                self.seed.fill_(int(seed))
+            limit = lens + max_new_tokens
+            self.prompt_len.copy_(lens)
+            self.limit.copy_(limit)
+            # a row whose budget is spent before the first emit launch has ended already
+            self.end.copy_(torch.where(limit <= n0, limit, torch.zeros_like(limit)))
+            if stop_bits is None:
+                self.stop_bits.zero_()
+            else:
+                self.stop_bits.copy_(stop_bits)
+            self.pad.fill_(int(pad))
+            self.idx[:, :Lmax].copy_(idx)
+            if want_lp:
+                self.logprob.zero_()
+            steps = 0
+            n = n0
+            if n0 < total:                             # else no column is left to decide
+                if n0 > self.T:                        # every prompt longer than the window: phase 2 only
+                    self.len.fill_(n0)
+                else:
+                    self.len.fill_(1)
+                    for _ in range(1, n0):             # no output needed yet: the no-head prefill step
+                        g1p.replay() if g1p else self._step1(False)
+                while n < total:
+                    if n <= self.T:
+                        g1.replay() if g1 else self._step1(True)
+                    else:
+                        g2.replay() if g2 else self._step2()
+                    n += 1
+                    steps += 1
+                    if poll_every and steps % poll_every == 0 and n < total and not bool((self.end == 0).any()):
+                        break
+            tokens = self.idx[:, :total].clone()
+            lengths = self.end.clone()
+            logprobs = self.logprob[:, :total].clone() if want_lp else None
+            # columns no step reached: pad / 0 (rows ended before n0 never met an emit launch either)
+            cols = torch.arange(total, device=self.dev)[None, :]
+            past = cols >= lengths[:, None]
+            tokens.masked_fill_(past, int(pad))
+            if want_lp:
+                logprobs.masked_fill_(past, 0.0)
+            return tokens, lengths, logprobs, steps
         finally:
             self.m.train(was_training)

@@ -556,3 +556,56 @@ class BigramLanguageModel(nn.Module):
                 idx_next = torch.multinomial(probs, num_samples=1, generator=generator)  # GPT1.py:208
             idx = torch.cat((idx, idx_next), dim=1)                     # GPT1.py:210
         return idx
+
+    # -- complete / score: ragged prompts, stop tokens, log-probs (decode.py's ragged mode) --------
+    def complete(self, prompts, max_new_tokens, *, stop_tokens=(), pad_token=0, return_logprobs=False, greedy=False,
+                 generator=None, temperature=1.0, top_k=None, top_p=1.0, poll_every=32):
+        """Continue several prompts of different lengths in one batch on the decode engine.
+
+        ``prompts``: a list of 1-D int64 tensors (each of length >= 1), or a pair ``(idx[B, Lmax],
+        lens[B])``.  Row b runs until it emits one of ``stop_tokens`` (the stop token is kept; one
+        inside a prompt does not count) or has ``max_new_tokens`` new tokens.  Returns
+        ``Completion(tokens, lengths, logprobs, steps)``: ``tokens`` [B, max(lens) + max_new_tokens]
+        with ``pad_token`` after each row's ``lengths[b]`` tokens; ``logprobs`` (``return_logprobs``)
+        the log-probability of every token from column 1 on under the model at temperature 1 without
+        cuts -- prompt tokens included -- and 0 in column 0 and the pad columns; ``steps`` the head
+        steps run (every ``poll_every`` steps the host asks whether a row still runs; 0: never).
+
+        Each row's tokens are those ``generate`` gives that row (same ``generator`` seed draw, same
+        sampling settings): rows advance in lock step and do not see each other.  ``pad_token`` must
+        be a token of the vocabulary: ended rows are still embedded while the others finish.  Needs a
+        GPU and the eval-mode forward (there is no literal-loop version)."""
+        from .completion import Completion, check_complete_args, pack_prompts, stop_words
+        from .sampling import check_sampling
+        cfg = self.config
+        neutral = check_sampling(temperature, top_k, top_p, greedy)
+        idx, lens = pack_prompts(prompts)
+        check_complete_args(idx, lens, max_new_tokens, pad_token, cfg.vocab_size, poll_every)
+        stop = stop_words(stop_tokens, cfg.vocab_size)
+        dev = self._store.master.device
+        if dev.type != "cuda":
+            raise RuntimeError("charpt: complete() runs the decode engine on an AMD GPU (HIP); there is no CPU "
+                               f"version (the model is on {dev})")
+        if self.training and cfg.dropout > 0:
+            raise RuntimeError("charpt: complete() computes the eval-mode forward only; call model.eval() first "
+                               "(dropout is on)")
+        from .decode import EMIT_DRAW, EMIT_FILTERED, EMIT_GREEDY, DecodeEngine
+        B, width = idx.shape[0], idx.shape[1] + int(max_new_tokens)
+        key = (B, width, bool(return_logprobs), dev)
+        cache = self.__dict__.setdefault("_complete_engines", {})
+        eng = cache.get(key)
+        if eng is None or eng.m is not self:
+            eng = cache[key] = DecodeEngine(self, B, width, ragged=True, logprobs=bool(return_logprobs))
+        seed = None if greedy else int(torch.randint(0, 2 ** 62, (1,), generator=generator))
+        mode = EMIT_GREEDY if greedy else (EMIT_DRAW if neutral else EMIT_FILTERED)
+        out = eng.complete(idx.to(dev), lens, int(max_new_tokens), mode=mode, seed=seed,
+                           sampling=None if neutral else (temperature, top_k, top_p), stop_bits=stop,
+                           pad=int(pad_token), poll_every=int(poll_every))
+        return Completion(*out)
+
+    def score(self, prompts):
+        """Log-probability of every token of every prompt given its last ``block_size`` predecessors
+        (the reference's crop, so text longer than the window is scored too): ``(logprobs [B,
+        max(lens)], lengths [B])``, column 0 and the columns past a row's length 0."""
+        out = self.complete(prompts, 0, return_logprobs=True, greedy=True)
+        return out.logprobs, out.lengths

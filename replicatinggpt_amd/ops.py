@@ -502,6 +502,37 @@ def decode_sample_filtered(logits: Tensor, params: Tensor, seed: Tensor, len_dev
             "decode_sample_filtered")
 
 
+@_op("decode_emit", ("end", "idx", "logprob"))
+def decode_emit(logits: Tensor, emit_mode: int, params: Optional[Tensor], seed: Tensor, len_dev: Tensor,
+                prompt_len: Tensor, limit: Tensor, end: Tensor, stop_bits: Tensor, pad: Tensor, idx: Tensor,
+                logprob: Optional[Tensor]) -> None:
+    """The ragged batch's per-row epilogue (include/charpt.h cg_decode_emit): forced prompt tokens, the
+    samplers' token (emit_mode 0 greedy, 1 plain draw, 2 filtered draw with params), stop tokens, the per-row
+    limit and, when logprob is given, the token's log-probability -- column *len_dev of idx / logprob.
+    (The C ABI's `mode` is `emit_mode` here: torch's functionalization wrapper of a mutating op has an
+    argument called `mode` of its own, and opcheck fails on the clash.)"""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("decode_emit: logits must be float32 [B, V] with unit column stride")
+    B, V = logits.shape
+    for t, name in ((prompt_len, "prompt_len"), (limit, "limit"), (end, "end")):
+        if t.dtype != torch.int64 or t.numel() != B or not t.is_contiguous():
+            raise ValueError(f"decode_emit: {name} must be {B} contiguous int64")
+    if stop_bits.dtype != torch.int64 or stop_bits.numel() < (V + 63) // 64 or not stop_bits.is_contiguous():
+        raise ValueError("decode_emit: stop_bits must be ceil(V / 64) contiguous 64-bit words (an int64 tensor)")
+    if pad.dtype != torch.int64 or pad.numel() != 1:
+        raise ValueError("decode_emit: pad must be one int64")
+    if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != B or idx.stride(1) != 1:
+        raise ValueError("decode_emit: idx must be int64 [B, ld] with unit column stride")
+    if logprob is not None and (logprob.dtype != torch.float32 or logprob.dim() != 2 or logprob.stride(1) != 1
+                                or logprob.stride(0) != idx.stride(0) or logprob.shape[0] != B):
+        raise ValueError("decode_emit: logprob must be float32 [B, ld] with idx's row stride")
+    if params is not None and (params.dtype != torch.float32 or params.numel() < 3 or not params.is_contiguous()):
+        raise ValueError("decode_emit: params must be three contiguous float32 (temperature, top_k, top_p)")
+    L.check(L.load().cg_decode_emit(L.ptr(logits), logits.stride(0), V, B, emit_mode, L.ptr(params), L.ptr(seed),
+                                    L.ptr(len_dev), L.ptr(prompt_len), L.ptr(limit), L.ptr(end), L.ptr(stop_bits),
+                                    L.ptr(pad), L.ptr(idx), idx.stride(0), L.ptr(logprob), _s(logits)), "decode_emit")
+
+
 # ---------------------------------------------------------------------------------------
 @_op("adamw", ("p", "m", "v", "p_bf16"))
 def adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, p_bf16: Optional[Tensor], lr: float, beta1: float, beta2: float,
