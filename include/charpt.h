@@ -219,6 +219,35 @@ int cg_reduce_rows_ex(const float* part, int64_t rows, int64_t N, float* out, in
 int cg_gemm(int op_dtype, int a_trans, int b_trans, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
             const void* B, int64_t ldb, void* C, int c_dtype, int64_t ldc, const cg_epilogue_t* epi, int split_k,
             void* workspace, void* stream);
+/* Several split-K weight gradients (dW = dy^T x) as ONE launch of the 128x128 persistent bf16 kernel
+   (the attention sublayer's projection and QKV weights: GPT1.py:111-112,136).  Problem i is the call
+       cg_gemm(CG_BF16, 1, 1, M, N, K, A, lda, B, ldb, C, CG_F32, ldc, {CG_EPI_STORE, beta, flags}, split_k,
+               workspace, stream)
+   -- A [K][M] and B [K][N] bf16, C [M][N] fp32 (+= beta C), split_k >= 2, workspace of
+   cg_gemm_workspace(M, N, split_k) bytes, flags CG_GEMM_SLAB_BF16 / CG_GEMM_DEFER_REDUCE -- and its C
+   equals that call's bit for bit; its slab reduce runs or stays pending as that call's would.  The
+   launch's item list is the problems' item lists one after the other, so splits chosen over the sum of
+   the problems' tiles fill the machine in one round where each problem alone could not.
+   cg_gemm_wgrad_group_supported: 1 if every problem is one the persistent kernel takes under the
+   current dispatch (M, N % 128 == 0, K % 64 == 0, no empty split, 16-B aligned operands, ld % 8 == 0)
+   and all use the same slab type; otherwise cg_gemm_wgrad_group returns CG_EINVAL and the caller
+   issues the cg_gemm calls.                                                                    */
+enum { CG_GEMM_GROUP_MAX = 4 };
+typedef struct {
+    int64_t M, N, K;
+    const void* A;
+    int64_t lda;
+    const void* B;
+    int64_t ldb;
+    float* C;
+    int64_t ldc;
+    float beta;
+    int split_k;
+    void* workspace;
+    int flags;                /* CG_GEMM_SLAB_BF16 | CG_GEMM_DEFER_REDUCE */
+} cg_wgrad_problem_t;
+int cg_gemm_wgrad_group_supported(const cg_wgrad_problem_t* problems, int n);
+int cg_gemm_wgrad_group(const cg_wgrad_problem_t* problems, int n, void* stream);
 /* A residual-stream GEMM with the LayerNorm that reads its output, in one launch (the attention
    projection + ln2, the FFN's second Linear + the next block's ln1 / ln_f: GPT1.py:136,145-147,
    159-160,163-164,173): out = resid + [dropout](A W^T + bias) (fp32; epi kind CG_EPI_BIAS_RESID or

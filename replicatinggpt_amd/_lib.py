@@ -28,6 +28,12 @@ class Epilogue(ctypes.Structure):
                 ("beta", c_flt), ("colpart", P), ("flags", c_int)]
 
 
+class WgradProblem(ctypes.Structure):
+    """cg_wgrad_problem_t: one weight gradient of a cg_gemm_wgrad_group launch."""
+    _fields_ = [("M", c_i64), ("N", c_i64), ("K", c_i64), ("A", P), ("lda", c_i64), ("B", P), ("ldb", c_i64), ("C", P),
+                ("ldc", c_i64), ("beta", c_flt), ("split_k", c_int), ("workspace", P), ("flags", c_int)]
+
+
 _SIGS = {
     "cg_last_error_string": (ctypes.c_char_p, []),
     "cg_version": (c_int, []),
@@ -71,6 +77,8 @@ _SIGS = {
     "cg_reduce_rows_ex": (c_int, [P, c_i64, c_i64, P, c_int, c_int, P]),
     "cg_gemm": (c_int, [c_int, c_int, c_int, c_i64, c_i64, c_i64, P, c_i64, P, c_i64, P, c_int, c_i64,
                         ctypes.POINTER(Epilogue), c_int, P, P]),
+    "cg_gemm_wgrad_group_supported": (c_int, [ctypes.POINTER(WgradProblem), c_int]),
+    "cg_gemm_wgrad_group": (c_int, [ctypes.POINTER(WgradProblem), c_int, P]),
     "cg_colsum_workspace": (c_i64, [c_i64, c_i64]),
     "cg_colsum": (c_int, [P, c_int, c_i64, c_i64, c_i64, P, c_int, P, P]),
     "cg_attn_fwd": (c_int, [c_int, c_i64, c_i64, c_i64, c_i64, P, P, P, c_i64, P, c_i64, P, c_flt, c_dbl, c_u64, P,

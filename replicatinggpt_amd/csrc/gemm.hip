@@ -285,3 +285,87 @@ extern "C" int cg_gemm(int op_dtype, int a_trans, int b_trans, int64_t M, int64_
     return CG_OK;
 }
 
+
+// ---- grouped split-K weight gradients (gemm_pk_group.hip) -----------------------------------------
+namespace {
+
+// cg_gemm's view of one problem of the group: what its slabs are and whether it applies at all
+struct GroupPlan {
+    bool ok, slab_bf16, defer;
+};
+GroupPlan plan_group_problem(const cg_wgrad_problem_t& p) {
+    GroupPlan g = {false, false, false};
+    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || !p.A || !p.B || !p.C || !p.workspace || p.split_k < 2 || p.split_k > 64)
+        return g;
+    if (p.flags & ~(CG_GEMM_SLAB_BF16 | CG_GEMM_DEFER_REDUCE)) return g;
+    if (g_skip_splitk_reduce || (((uintptr_t)p.workspace) & 15)) return g;
+    if (!gemm_wgrad_group_ok(p.M, p.N, p.K, p.A, p.lda, p.B, p.ldb, p.C, p.ldc, p.split_k)) return g;
+    // (the shape conditions above make cg_gemm's vec4 true)
+    g.ok = true;
+    g.slab_bf16 = (p.flags & CG_GEMM_SLAB_BF16) && p.ldc == p.N && (p.M * p.N) % 8 == 0;
+    g.defer = (p.flags & CG_GEMM_DEFER_REDUCE) && p.ldc == p.N &&
+              (int64_t)p.split_k * p.M * p.N * 4 <= ((int64_t)40 << 20);
+    return g;
+}
+
+bool plan_group(const cg_wgrad_problem_t* probs, int n, GroupPlan* plans) {
+    if (!probs || n < 1 || n > MAX_GROUP) return false;
+    int64_t items = 0;
+    for (int i = 0; i < n; ++i) {
+        plans[i] = plan_group_problem(probs[i]);
+        if (!plans[i].ok || plans[i].slab_bf16 != plans[0].slab_bf16) return false;   // one slab type per launch
+        items += (probs[i].M / 128) * (probs[i].N / 128) * probs[i].split_k;
+    }
+    return items < ((int64_t)1 << 30);
+}
+
+}  // namespace
+
+extern "C" int cg_gemm_wgrad_group_supported(const cg_wgrad_problem_t* probs, int n) {
+    GroupPlan plans[MAX_GROUP];
+    return plan_group(probs, n, plans) ? 1 : 0;
+}
+
+extern "C" int cg_gemm_wgrad_group(const cg_wgrad_problem_t* probs, int n, void* stream) {
+    GroupPlan plans[MAX_GROUP];
+    CG_REQUIRE(plan_group(probs, n, plans),
+               "cg_gemm_wgrad_group: unsupported group (cg_gemm_wgrad_group_supported: 1..%d bf16 problems the "
+               "128x128 persistent kernel takes at split_k >= 2, one slab type)", MAX_GROUP);
+    hipStream_t st = (hipStream_t)stream;
+    GroupProb gp[MAX_GROUP];
+    for (int i = 0; i < n; ++i) {
+        const cg_wgrad_problem_t& p = probs[i];
+        GroupProb& q = gp[i];
+        q = GroupProb{};
+        q.A = (const bf16_t*)p.A;
+        q.B = (const bf16_t*)p.B;
+        q.ws = p.workspace;
+        q.lda = p.lda;
+        q.ldb = p.ldb;
+        q.M = (int)p.M;
+        q.N = (int)p.N;
+        q.tilesN = (int)(p.N / 128);
+        q.ntiles = (int)(p.M / 128) * q.tilesN;
+        q.nkt = (int)(p.K / 64);
+        q.nkc = (q.nkt + p.split_k - 1) / p.split_k;
+        q.split_k = p.split_k;
+    }
+    pk_group_launch(gp, n, plans[0].slab_bf16, st);
+    // each problem's reduce: deferred or launched exactly as cg_gemm does after its own launch
+    for (int i = 0; i < n; ++i) {
+        const cg_wgrad_problem_t& p = probs[i];
+        if (plans[i].defer) {
+            std::lock_guard<std::mutex> lk(defer_mutex());
+            DeferQueue& q = *defer_queue(st, true);
+            if (q.nred == MAX_RED) flush_red_locked(q);
+            q.red[q.nred++] = RedJob{(const float*)p.workspace, p.C, p.M * p.N / 4, p.split_k, p.beta, plans[i].slab_bf16};
+        } else {
+            EpiArgs e = make_epi(nullptr);
+            e.beta = p.beta;
+            e.slab_bf16 = plans[i].slab_bf16;
+            launch_splitk_reduce(p.workspace, p.split_k, p.M, p.N, p.C, CG_F32, p.ldc, e, true, st);
+        }
+    }
+    CG_LAUNCH_CHECK("cg_gemm_wgrad_group");
+    return CG_OK;
+}

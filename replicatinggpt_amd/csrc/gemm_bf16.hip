@@ -232,6 +232,18 @@ bool gemm_rowdot_supported(int at, int bt, int64_t M, int64_t N, int64_t K, int6
     return fast_shape_ok(M, N, K, lda, ldb, ldc, 1) && rowdot_ok(pick_variant(at, bt, M, N, 1), at, 1, N);
 }
 
+// a TN split-K product that fast_gemm_launch would hand to the 128x128 persistent kernel's slab epilogue
+// (the same conditions, in its order)
+bool gemm_wgrad_group_ok(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb,
+                         const void* C, int64_t ldc, int split_k) {
+    if (split_k < 2 || !fast_shape_ok(M, N, K, lda, ldb, ldc, split_k)) return false;
+    if ((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C)) & 15) return false;
+    if (pick_variant(1, 1, M, N, split_k) != 9) return false;   // the 2-stage 128x128 persistent kernel only
+    const int64_t nkt = K / FBK, nkc = (nkt + split_k - 1) / split_k;
+    if ((split_k - 1) * nkc >= nkt) return false;   // an empty last split
+    return M * N < ((int64_t)1 << 31) && K < ((int64_t)1 << 31);
+}
+
 bool fast_gemm_launch(int at, int bt, int64_t M, int64_t N, int64_t K, const bf16_t* A, int64_t lda, const bf16_t* B,
                       int64_t ldb, void* C, int c_dtype, int64_t ldc, const EpiArgs& e, int split_k, float* ws,
                       hipStream_t st) {

@@ -324,6 +324,30 @@ bool pk_gemm_launch(int variant, int at, int bt, int64_t M, int64_t N, int64_t K
                     const bf16_t* B, int64_t ldb, void* C, int c_dtype, int64_t ldc, const EpiArgs& e, int split_k,
                     float* ws, hipStream_t st);
 
+// One problem of a grouped split-K weight-gradient launch (cg_gemm_wgrad_group; gemm_pk_group.hip):
+// slabs[s][M][N] = sum over split s's K-tiles of A[k][m] B[k][n].  The caller fills everything but
+// item0 and gm (pk_group_launch's).
+constexpr int MAX_GROUP = 4;
+struct GroupProb {
+    const bf16_t* A;   // [K][M], row stride lda
+    const bf16_t* B;   // [K][N], row stride ldb
+    void* ws;          // split_k slabs of M x N, fp32 or bf16
+    int64_t lda, ldb;
+    int M, N;
+    int tilesN, ntiles;   // 128 x 128 output tiles: per row panel, in all
+    int nkt, nkc;         // 64-deep K-tiles: in all, per split (the last split may be shorter)
+    int split_k;
+    int item0;            // first item of this problem in the launch's item list
+    int gm;               // tile order (gemm_tile.h tile_rc)
+};
+// whether the 128x128 persistent kernel would run this weight gradient at this split (>= 2) under the
+// current dispatch: cg_gemm's own conditions for it (gemm_bf16.hip)
+bool gemm_wgrad_group_ok(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb,
+                         const void* C, int64_t ldc, int split_k);
+// one launch for all problems (bf16 slabs or fp32 slabs for every one of them); takes the stream's pending
+// deferred work as a single-problem launch does
+void pk_group_launch(const GroupProb* probs, int n, bool slab_bf16, hipStream_t st);
+
 // persistent 8-wave LDS-DMA kernels (gemm_p8.hip), variant >= 20 (20 = automatic tile choice)
 // gemm_ln.hip: the residual GEMM + next LayerNorm kernel (N = 384 row panels)
 bool gemm_resid_ln_supported(int64_t M, int64_t N, int64_t K);

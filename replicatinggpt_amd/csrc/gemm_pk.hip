@@ -54,60 +54,12 @@ __device__ __forceinline__ void bounds_chk(const void* p, int bytes, const void*
 }
 #endif
 
+#include "gemm_pk.h"
+
 namespace cg {
 int g_pk_flags = 0;  // cg_set_tuning("pk_flags"): bit 0 = drain epilogue stores each step, bit 1 = per-fragment epilogue
 namespace {
 using namespace gt;
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// per-lane part of one operand's LDS-DMA sources: R rows (K-contiguous) or R columns (TR) x BK k
-template <bool TR, int R, int WAVES, int BK>
-struct DmaP {
-    static constexpr int INSTR = R * BK * 2 / 1024;  // 1-KB wave instructions per K-tile
-    static constexpr int PER_WAVE = INSTR / WAVES;
-    static_assert(PER_WAVE * WAVES == INSTR, "tile/wave mismatch");
-    static_assert(!TR || R >= 128, "transposed image swizzle needs >= 16 chunks per row");
-    uint32_t off[PER_WAVE];  // byte offset of this lane's 16-B chunk from the tile origin
-    int64_t kstep;
-#ifdef CG_PK_BOUNDS
-    const void* lo = nullptr;
-    const void* hi = nullptr;
-    int slot = 0;
-#endif
-
-    __device__ __forceinline__ void init(int64_t ld, int wave, int lane) {
-#pragma unroll
-        for (int i = 0; i < PER_WAVE; ++i) {
-            const int pos = (wave * PER_WAVE + i) * 1024 + lane * 16;
-            if (!TR) {
-                const int r = BK == 64 ? pos >> 7 : pos >> 6;
-                const int c = BK == 64 ? ((pos >> 4) & 7) ^ row_swz(r) : ((pos >> 4) & 3) ^ row_swz32(r);
-                off[i] = 2u * (uint32_t)((int)(r * ld) + c * 8);
-            } else {
-                const int k = pos / (2 * R), c = ((pos % (2 * R)) >> 4) ^ col_swz(k);
-                off[i] = 2u * (uint32_t)((int)(k * ld) + c * 8);
-            }
-        }
-        kstep = TR ? (int64_t)BK * ld : (int64_t)BK;
-    }
-    // instruction i (0..PER_WAVE-1) of one K-tile, from that K-tile's (wave-uniform) base address into
-    // the image at 32-bit LDS address img: the saddr form (SGPR base + per-lane byte offset) and an
-    // SGPR LDS address.  With a generic image pointer and a 64-bit lane address hipcc spent ~6
-    // instructions per DMA (two 64-bit VALU adds, two v_readfirstlane, a null-pointer select) on a
-    // VALU -> SGPR -> m0 dependency chain.
-    __device__ __forceinline__ void issue1(const bf16_t* base, int i, uint32_t img, int wave) const {
-#ifdef CG_PK_BOUNDS
-        bounds_chk((const char*)base + off[i], 16, lo, hi, slot);
-#endif
-        dma16sl(base, off[i], img + (uint32_t)((wave * PER_WAVE + i) * 1024));
-    }
-};
 
 __device__ __forceinline__ float rbf(float x) { return bf2f(f2bf(x)); }
 
@@ -408,20 +360,6 @@ __device__ __forceinline__ void epi_resid_nj(fv4 (&acc)[4][NJ], int64_t mr, int6
             st_out16((float4*)(C + (mr + 16 * i) * ldc + nc + 16 * j), make_float4(v[0], v[1], v[2], v[3]));
         }
 }
-
-// Wave grid: 64 x 64 wave tiles, except BN = 96 (two 64 x 48 wave tiles per 64-row band: NJ = 3
-// fragments of 16 columns instead of 4).
-template <int BM, int BN, int NBUF, int BK = FBK>
-struct GeoP {
-    static constexpr int WM = BM / 64, WN = BN == 96 ? 2 : BN / 64, WAVES = WM * WN, THREADS = WAVES * 64;
-    static constexpr int WTN = BN / WN, NJ = WTN / 16;   // wave tile columns, 16-column fragments per wave
-    static_assert(WTN == 64 || WTN == 48, "wave tile");
-    static constexpr int IMG_A = BM * BK * 2, IMG_B = BN * BK * 2, STAGE = IMG_A + IMG_B;
-    static constexpr int LDS = NBUF * STAGE;
-    static constexpr int OCC_LDS = (160 * 1024) / LDS;
-    static constexpr int OCC = OCC_LDS > 4 ? 4 : (OCC_LDS < 1 ? 1 : OCC_LDS);  // resident blocks per CU (LDS-bound)
-    static constexpr int WPE = (WAVES * OCC + 3) / 4;   // waves per SIMD
-};
 
 // EK: the item epilogue.  EK_SLAB = split-K (split_k > 1, fp32 slab stores only), 0..5 = one
 // CG_EPI_* kind fixed at compile time, EK_ANY = every kind, beta and the per-fragment form at run

@@ -377,6 +377,22 @@ def _gemm_slots():
     return _SLOTS[dev]
 
 
+def _split_for_tiles(tiles, nkt, slots=None):
+    """_wgrad_split's cost expression for ``tiles`` 128x128 output tiles of ``nkt`` K-tiles -- one
+    product's, or the sum over the products of one grouped launch (linear_wgrad_group) -- on ``slots``
+    resident blocks (default: the current device's)."""
+    slots = slots or _gemm_slots()
+    best, best_cost = 1, None
+    for split in range(1, 33):
+        per = -(-nkt // split)
+        if (split - 1) * per >= nkt or per < 4:   # an empty last split / too little depth
+            continue
+        cost = -(-tiles * split // slots) * per * (1 + split / 50)
+        if best_cost is None or cost < best_cost:
+            best, best_cost = split, cost
+    return best
+
+
 def _wgrad_split(M, N, K, fast):
     """Split-K factor of a weight-gradient GEMM (K = tokens).  bf16 path: the persistent kernel
     hands each resident block ceil(items / slots) items of ceil(K-tiles / split) reduction depth
@@ -386,17 +402,7 @@ def _wgrad_split(M, N, K, fast):
     within 3 % of the measured best of each (tools/gemm_scan2.py, profiles/r2_gemm_scan_wgrad_splits.txt;
     the power-of-two splits of round 1 were up to 25 % slower)."""
     if fast:
-        tiles, slots = -(-M // 128) * -(-N // 128), _gemm_slots()
-        nkt = K // 64
-        best, best_cost = 1, None
-        for split in range(1, 33):
-            per = -(-nkt // split)
-            if (split - 1) * per >= nkt or per < 4:   # an empty last split / too little depth
-                continue
-            cost = -(-tiles * split // slots) * per * (1 + split / 50)
-            if best_cost is None or cost < best_cost:
-                best, best_cost = split, cost
-        return best
+        return _split_for_tiles(-(-M // 128) * -(-N // 128), K // 64)
     tiles = -(-M // 64) * -(-N // 64)
     split = 1
     while tiles * split * 2 <= 1024 and split < 32 and K % (64 * split * 2) == 0 and K // (split * 2) >= 256:
@@ -411,13 +417,27 @@ def _wgrad_split(M, N, K, fast):
 SLAB_BF16 = os.environ.get("CHARPT_SLAB_BF16", "1") != "0"
 
 
-def linear_wgrad(dy2, x2, out, beta, into_slot=False):
+def linear_wgrad(dy2, x2, out, beta, into_slot=False, group=None, last=True):
     """out[N,K] (+)= dy2[M,N]^T @ x2[M,K]   (fp32, deterministic split-K).
 
     into_slot: ``out`` is a region's flat gradient slot, which nothing reads before DEFER closes,
     so inside ``with DEFER:`` its split-K reduce may stay pending past this call.  Any other
     output (a temporary, a tensor handed to autograd) gets its pending reduces flushed right after
-    the GEMM, so it is complete when this returns.  Slot outputs use bf16 split-K slabs (SLAB_BF16)."""
+    the GEMM, so it is complete when this returns.  Slot outputs use bf16 split-K slabs (SLAB_BF16).
+
+    group: a list that collects a sublayer's weight gradients for one launch (linear_wgrad_group):
+    with last=False the product is only held in it, the call with last=True issues everything held."""
+    if group is not None:
+        group.append((dy2, x2, out, beta, into_slot))
+        if last:
+            held = list(group)
+            group.clear()
+            linear_wgrad_group(held)
+        return out
+    return _wgrad_single(dy2, x2, out, beta, into_slot)
+
+
+def _wgrad_single(dy2, x2, out, beta, into_slot):
     if "skip_wgrad" in WHATIF:
         return out
     M, N = dy2.shape
@@ -436,6 +456,54 @@ def linear_wgrad(dy2, x2, out, beta, into_slot=False):
     ops.gemm(dy2, x2, out, _is_bf16(dy2.dtype), True, True, N, K, M, N, K, out.stride(0), L.EPI_STORE, None,
              None, 0, None, 0, 0.0, 0, None, 0, float(beta), split, ws, flags)
     return out
+
+
+# One split-K launch per sublayer for its two weight gradients (cg_gemm_wgrad_group), the split chosen over
+# the sum of their tiles: the attention sublayer's projection + QKV pair (9 + 27 tiles at C2: split 14,
+# 504 items in one round, instead of 32 and 18 in two launches), and the FeedForward's W2 + W1 pair (72
+# tiles: split 7 instead of 14 and 14, half the slab bytes).  C2 step 2.8115 -> 2.7690 ms with the attention
+# pair, 2.7461 ms with both (profiles/wgrad_group_ab.txt).  CHARPT_WGRAD_GROUP=0 / CHARPT_WGRAD_GROUP_FFN=0:
+# the single launches (A/B).
+WGRAD_GROUP = int(os.environ.get("CHARPT_WGRAD_GROUP", "1") != "0")
+WGRAD_GROUP_FFN = int(os.environ.get("CHARPT_WGRAD_GROUP_FFN", "1") != "0")
+
+
+def _wgrad_group_on(act):
+    """Whether a bf16 sublayer holds its first weight gradient for a grouped launch: the switch, one
+    stream, and a library that has the entry point (an A/B build of an older tree keeps its own order)."""
+    return bool(WGRAD_GROUP) and not SIDE.enabled and _is_bf16(act) and hasattr(L.load(), "cg_gemm_wgrad_group")
+
+
+def linear_wgrad_group(items):
+    """linear_wgrad for every (dy2, x2, out, beta, into_slot) of ``items`` -- as ONE launch where the
+    library takes the group (bf16 products over the same tokens, all into slots or none, a common split
+    >= 2 from _wgrad_split's cost over the sum of their tiles); each out then has the bits linear_wgrad
+    gives at that split.  Otherwise one launch each."""
+    if "skip_wgrad" in WHATIF:
+        return
+    M = items[0][0].shape[0]
+    same = all(dy.shape[0] == M and x.shape[0] == M and it[4] == items[0][4] for it in items for dy, x in [it[:2]])
+    fast = same and all(_is_bf16(dy.dtype) and _is_bf16(x.dtype) and dy.shape[1] % 128 == 0 and x.shape[1] % 128 == 0
+                        for dy, x, *_ in items) and M % 64 == 0
+    if fast and 1 < len(items) <= 4:
+        tiles = sum((dy.shape[1] // 128) * (x.shape[1] // 128) for dy, x, *_ in items)
+        split = _split_for_tiles(tiles, M // 64)
+        into_slot = items[0][4]
+        if split > 1:
+            dys, xs, outs = [it[0] for it in items], [it[1] for it in items], [it[2] for it in items]
+            betas, splits = [float(it[3]) for it in items], [split] * len(items)
+            wss = [torch.empty(ops.gemm_workspace(dy.shape[1], x.shape[1], split) // 4, dtype=torch.float32,
+                               device=dy.device) for dy, x in zip(dys, xs)]
+            defer = DEFER.active and into_slot
+            flags = (L.GEMM_SLAB_BF16 if SLAB_BF16 and into_slot else 0) | (L.GEMM_DEFER_REDUCE if defer else 0)
+            if ops.gemm_wgrad_group_supported(dys, xs, outs, wss, betas, splits, flags):
+                if defer:   # the reduces may run after this call returns
+                    DEFER.keep.extend((*wss, *dys, *xs))
+                    DEFER.note_stream()
+                ops.gemm_wgrad_group(dys, xs, outs, wss, betas, splits, flags)
+                return
+    for dy, x, out, beta, into_slot in items:
+        _wgrad_single(dy, x, out, beta, into_slot)
 
 
 def _colpart_ok(dy2, w, aux, out_ld):
@@ -745,9 +813,13 @@ class AttnSublayerFn(torch.autograd.Function):
         # proj: dW = dy^T o, db = colsum(dy) (side stream, unless fused upstream), do = dy W
         g_pw, beta_pw, f_pw = proj_w.grad_target()
         g_pb, beta_pb, f_pb = proj_b.grad_target()
+        # with WGRAD_GROUP the projection's weight gradient waits for dqkv and goes out with the QKV one
+        g, beta, f_qkv = qkv_w.grad_target()
+        group = _wgrad_group_on(act) and g_pw is not None and g is not None
+        held = [] if group else None
         with SIDE.run(dev, dy, o):
             if g_pw is not None:
-                linear_wgrad(dy, o, g_pw, beta_pw, g_pw is proj_w.slot)
+                linear_wgrad(dy, o, g_pw, beta_pw, g_pw is proj_w.slot, held, False)
             if g_pb is not None and not bias_done:
                 colsum_into(dy, g_pb, beta_pb)
         do = torch.empty((B * T, C), dtype=act, device=x2.device)
@@ -761,15 +833,19 @@ class AttnSublayerFn(torch.autograd.Function):
                                   T, delta)
         else:
             linear_dgrad(dy, wp, do)
-        EARLY.region_done(proj_w, g_pw, beta_pw)   # the projection weight's last read this step
+        if not group:
+            EARLY.region_done(proj_w, g_pw, beta_pw)   # the projection weight's last read this step
         dqkv = attention_bwd(qkv, B, T, lc.n_head, lc.head_size, o, do, lse, lc.scale, lc.p, lc.seed, lc.rng_call,
                              lc.site, ctx.mask, delta)
-        g, beta, f_qkv = qkv_w.grad_target()
         if g is not None:
+            # the pair goes out before the QKV dgrad, whose launch then hosts both reduces on its free slots
+            # (after it the reduces had no host before the AdamW queue needed them: 2.8417 vs 2.7690 ms/step)
             with SIDE.run(dev, dqkv, a):
-                linear_wgrad(dqkv, a, g, beta, g is qkv_w.slot)
+                linear_wgrad(dqkv, a, g, beta, g is qkv_w.slot, held)
         da = torch.empty((B * T, C), dtype=act, device=x2.device)
         linear_dgrad(dqkv, qkv_w.operand(act), da)
+        if group:   # the projection's gradient is final with the group (its update moves with it)
+            EARLY.region_done(proj_w, g_pw, beta_pw)
         EARLY.region_done(qkv_w, g, beta)
         dx, _, f_ln = layernorm_bwd(da, x2, ln_w, ln_b, mean, rstd, dres=d32, link=ctx.in_link)
         return (dx.view(B, T, C), None, None, None, None, None, None, *f_ln, *f_qkv(), *f_pw(), *f_pb())
@@ -890,13 +966,16 @@ class FFNSublayerFn(torch.autograd.Function):
         dev = x2.device
         g_w2, beta_w2, f_w2 = w2.grad_target()
         g_b2, beta_b2, f_b2 = b2.grad_target()
+        g_w1, beta_w1, f_w1 = w1.grad_target()
+        # with WGRAD_GROUP_FFN W2's weight gradient waits for dz1 and goes out with W1's
+        group = bool(WGRAD_GROUP_FFN) and _wgrad_group_on(act) and g_w2 is not None and g_w1 is not None
+        held = [] if group else None
         with SIDE.run(dev, dz2, h):
             if g_w2 is not None:
-                linear_wgrad(dz2, h, g_w2, beta_w2, g_w2 is w2.slot)
+                linear_wgrad(dz2, h, g_w2, beta_w2, g_w2 is w2.slot, held, False)
             if g_b2 is not None and not bias_done:
                 colsum_into(dz2, g_b2, beta_b2)
         dz1 = torch.empty_like(h)
-        g_w1, beta_w1, f_w1 = w1.grad_target()
         g_b1, beta_b1, f_b1 = b1.grad_target()
         part = None
         if g_b1 is not None and _colpart_ok(dz2, w2.operand(act), h, dz1.stride(0)):
@@ -910,10 +989,11 @@ class FFNSublayerFn(torch.autograd.Function):
                                       mk, mk.stride(0), part)
         else:
             linear_dgrad(dz2, w2.operand(act), dz1, "relu_bwd", aux=h if bits is None else bits)
-        EARLY.region_done(w2, g_w2, beta_w2)   # W2's gradient is final (its reduce went with this dgrad)
+        if not group:
+            EARLY.region_done(w2, g_w2, beta_w2)   # W2's gradient is final (its reduce went with this dgrad)
         with SIDE.run(dev, dz1, a, part):
             if g_w1 is not None:
-                linear_wgrad(dz1, a, g_w1, beta_w1, g_w1 is w1.slot)
+                linear_wgrad(dz1, a, g_w1, beta_w1, g_w1 is w1.slot, held)
             if g_b1 is not None:
                 if part is not None:
                     with DEFER.partials(part) if g_b1 is b1.slot else contextlib.nullcontext(False) as queued:
@@ -922,6 +1002,8 @@ class FFNSublayerFn(torch.autograd.Function):
                     colsum_into(dz1, g_b1, beta_b1)
         da = torch.empty((B * T, C), dtype=act, device=x2.device)
         linear_dgrad(dz1, w1.operand(act), da)
+        if group:
+            EARLY.region_done(w2, g_w2, beta_w2)
         EARLY.region_done(w1, g_w1, beta_w1)
         dx, _, f_ln = layernorm_bwd(da, x2, ln_w, ln_b, mean, rstd, dres=d32, link=ctx.in_link)
         return (dx.view(B, T, C), None, None, None, None, None, None, None, *f_ln, *f_w1(), *f_b1(), *f_w2(),

@@ -192,6 +192,45 @@ def gemm(a: Tensor, b: Tensor, out: Tensor, op_bf16: bool, a_trans: bool, b_tran
             "gemm")
 
 
+def _wgrad_problems(dy: List[Tensor], x: List[Tensor], out: List[Tensor], ws: List[Tensor], betas: List[float],
+                    splits: List[int], flags: int):
+    """The cg_wgrad_problem_t array of out[i][N, K] (+)= dy[i][M, N]^T @ x[i][M, K]."""
+    n = len(dy)
+    arr = (L.WgradProblem * n)()
+    for i in range(n):
+        M, N = dy[i].shape
+        K = x[i].shape[1]
+        lda, ldb, ldc = dy[i].stride(0), x[i].stride(0), out[i].stride(0)
+        _gemm_extents(dy[i], x[i], out[i], True, True, N, K, M, lda, ldb, ldc, "gemm_wgrad_group")
+        arr[i] = L.WgradProblem(N, K, M, dy[i].data_ptr(), lda, x[i].data_ptr(), ldb, out[i].data_ptr(), ldc,
+                                betas[i], splits[i], ws[i].data_ptr(), flags)
+    return arr, n
+
+
+def gemm_wgrad_group_supported(dy, x, out, ws, betas, splits, flags):
+    """Whether gemm_wgrad_group takes these weight gradients as one launch (cg_gemm_wgrad_group_supported:
+    asked from the library, current tuning knobs included; False for a library without the entry point)."""
+    lib = L.load()
+    if not hasattr(lib, "cg_gemm_wgrad_group_supported") or not 1 <= len(dy) <= 4:
+        return False
+    if any(t.dtype != torch.bfloat16 or t.stride(1) != 1 for t in (*dy, *x)):
+        return False
+    if any(t.dtype != torch.float32 or t.stride(1) != 1 for t in out) or any(w is None for w in ws):
+        return False
+    arr, n = _wgrad_problems(dy, x, out, ws, betas, splits, flags)
+    return bool(lib.cg_gemm_wgrad_group_supported(arr, n))
+
+
+@_op("gemm_wgrad_group", ("out", "ws"))
+def gemm_wgrad_group(dy: List[Tensor], x: List[Tensor], out: List[Tensor], ws: List[Tensor], betas: List[float],
+                     splits: List[int], flags: int) -> None:
+    """out[i][N, K] (+)= dy[i][M, N]^T @ x[i][M, K] for every i as ONE split-K launch (cg_gemm_wgrad_group):
+    each out[i] has the bits of gemm() at splits[i] with the same flags.  Fails (CG_EINVAL) unless
+    gemm_wgrad_group_supported."""
+    arr, n = _wgrad_problems(dy, x, out, ws, betas, splits, flags)
+    L.check(L.load().cg_gemm_wgrad_group(arr, n, _s(out[0])), "gemm_wgrad_group")
+
+
 @_op("gemm_bias_relu_bits", ("out", "bits"))
 def gemm_bias_relu_bits(a: Tensor, b: Tensor, out: Tensor, M: int, N: int, K: int, lda: int, ldb: int, ldc: int,
                         bias: Tensor, bits: Tensor, ld_bits: int) -> None:
