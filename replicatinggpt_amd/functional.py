@@ -603,9 +603,18 @@ def layernorm_bwd(dy2, x2, w_reg, b_reg, mean, rstd, dres=None, want_lp=False, l
     lp = torch.empty((rows, C), dtype=torch.bfloat16, device=dev) if (want_lp or use_link) else None
     gw, bw, fw = w_reg.grad_target()
     gb, bb, fb = b_reg.grad_target()
+    if gw is not None and gb is not None and bool(bw) != bool(bb):
+        # the library has one accumulate flag for the two (cg_layernorm_bwd_ex, cg_layernorm_bwd_reduce_ex):
+        # when only one of them accumulates, the other starts from zeros -- adding to 0 is exact
+        (gb if bw else gw).zero_()
+        bw = bb = 1.0
     gcs, bcs, fcs = None, 0.0, None
     if use_link and link.bias is not None and link.bias.slot is not None:
         gcs, bcs, fcs = link.bias.grad_target()
+        if gcs is not link.bias.slot:
+            # a temporary (the bias's .grad was assigned from outside) would be lost here: only the
+            # consumer's own backward can hand one to autograd, so it computes these column sums itself
+            gcs, bcs, fcs = None, 0.0, None
     ws = torch.empty(ops.layernorm_bwd_workspace(rows, C) // 4 + 1, dtype=torch.float32, device=dev)
     p = float(link.p) if use_link else 0.0
     seed, rng, site = (int(link.seed) if use_link else 0), (link.rng_call if (use_link and p > 0) else None), \
