@@ -28,6 +28,15 @@
  *     queue registry, so host threads that each drive their own stream are safe; two threads
  *     sharing one stream must order their calls themselves, as with any stream.  Until the flush,
  *     the caller keeps every queued job's workspace alive and reads none of its outputs.
+ *   - memory footprint: a call writes only the listed elements of its outputs (rows r, columns 0..width-1
+ *     at r * ld; never the ld - width padding of a row, nor past the last row) and only the bytes its
+ *     *_workspace() function states of its workspace; it reads nothing outside the logical extent of its
+ *     inputs whose value can affect the result (so padding and neighbouring memory may hold anything, NaN
+ *     included); it never modifies a const operand; and what outputs (where it writes, not accumulates)
+ *     and workspaces hold on entry is irrelevant: a workspace needs no initialisation.  A call refused
+ *     with CG_EINVAL for its shapes, strides or alignment has written nothing.
+ *     tests/test_gpu_footprint.py holds the training-path entry points to this on guard-banded, padded
+ *     and misaligned operands.
  *   - cg_last_error_string() is per thread.
  *   - return CG_OK (0) or an error code; cg_last_error_string() gives the message.
  *   - dtype codes: CG_F32 = 0 (float), CG_BF16 = 1 (bfloat16 bits, RNE rounding).
@@ -47,8 +56,9 @@ enum { CG_F32 = 0, CG_BF16 = 1 };
 /* cg_epilogue_t.aux_dtype only: ReLU keep bits, uint32 words [M][ld_aux], bit n % 32 of word n / 32
    of row m = (bf16 ReLU output (m, n) != 0).  CG_EPI_BIAS_RELU WRITES them (aux is an output there),
    CG_EPI_RELU_BWD reads them instead of the bf16 ReLU output (1/16 of its bytes).  Only where
-   cg_gemm_relu_bits_supported() says so (bf16, split 1, beta 0, N % 64 == 0, persistent kernels);
-   elsewhere cg_gemm returns CG_EINVAL. */
+   cg_gemm_relu_bits_supported() says so (bf16, split 1, beta 0, N % 64 == 0, persistent kernels) and
+   the words are 8-B aligned with an even ld_aux (a row's 64 columns are one 8-B access); elsewhere
+   cg_gemm returns CG_EINVAL. */
 enum { CG_BITS = 2 };
 
 /* GEMM epilogues (applied to acc = sum_k A(m,k) B(n,k), per output element (m,n)) */

@@ -8,10 +8,12 @@ using namespace cg;
 
 namespace {
 
-bool fast_attn_ok(int dtype, int64_t T, int64_t D, const void* a, const void* b, const void* c, int64_t ld1,
-                  int64_t ld2) {
-    return dtype == CG_BF16 && D == 64 && T % 64 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0 &&
-           ld1 % 8 == 0 && ld2 % 8 == 0;
+// (every pointer the MFMA kernels read or write in 16-B segments: q, k, v each on their own, since the
+// ABI takes them as three pointers)
+bool fast_attn_ok(int dtype, int64_t T, int64_t D, const void* a, const void* b, const void* c, const void* e,
+                  int64_t ld1, int64_t ld2) {
+    return dtype == CG_BF16 && D == 64 && T % 64 == 0 &&
+           (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)e) & 15) == 0 && ld1 % 8 == 0 && ld2 % 8 == 0;
 }
 
 // the backward workspace: delta = rowsum(dO * O) rounded up to 256 B, then a keep-bit image
@@ -24,7 +26,7 @@ int attn_fwd_impl(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const v
     CG_REQUIRE(dropout_p >= 0 && dropout_p < 1, "cg_attn_fwd: dropout_p must be in [0,1)");
     hipStream_t st = (hipStream_t)stream;
     DropArgs d = attn::make_drop(dropout_p, seed, rng_call, site);
-    if (fast_attn_ok(dtype, T, D, q, k, o, ld_qkv, ld_o)) {
+    if (fast_attn_ok(dtype, T, D, q, k, v, o, ld_qkv, ld_o)) {
         if (d.thr) {
             CG_REQUIRE(mask, "cg_attn_fwd: dropout on the MFMA path needs a mask buffer (cg_attn_mask_bytes)");
             if (!mask_ready) attn::launch_dropmask(B, H, T, mask, d, st);
@@ -53,8 +55,8 @@ int attn_bwd_impl(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const v
     hipStream_t st = (hipStream_t)stream;
     DropArgs d = attn::make_drop(dropout_p, seed, rng_call, site);
     float* delta = (float*)workspace;
-    const bool fast = fast_attn_ok(dtype, T, D, q, dout, dq, ld_qkv, ld_do) && ld_dqkv % 8 == 0 &&
-                      ((((uintptr_t)dk) | ((uintptr_t)dv) | ((uintptr_t)o)) & 15) == 0 && ld_o % 8 == 0;
+    const bool fast = fast_attn_ok(dtype, T, D, q, k, v, dout, ld_qkv, ld_do) && ld_dqkv % 8 == 0 &&
+                      ((((uintptr_t)dq) | ((uintptr_t)dk) | ((uintptr_t)dv) | ((uintptr_t)o)) & 15) == 0 && ld_o % 8 == 0;
     if (fast) {
         // delta = rowsum(dO * O) is computed inside the dQ kernel (which runs before dK/dV)
         if (d.thr) {

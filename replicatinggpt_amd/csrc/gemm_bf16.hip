@@ -251,7 +251,10 @@ bool fast_gemm_launch(int at, int bt, int64_t M, int64_t N, int64_t K, const bf1
     if ((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C)) & 15) return false;
     if (e.bias && (((uintptr_t)e.bias) & 15)) return false;
     if (e.resid && ((((uintptr_t)e.resid) & 15) || e.ld_resid % 4)) return false;
-    if (e.aux && ((((uintptr_t)e.aux) & 15) || e.ld_aux % 8)) return false;
+    // aux rows: 16-B segments of the bf16 / fp32 ReLU output, or 8-B word pairs of CG_BITS keep bits (one
+    // uint2 per row and 64 columns: relu_bits_store and the readers), whose rows need only an even word stride
+    const bool aux_bits = e.aux_dtype == CG_BITS;
+    if (e.aux && ((((uintptr_t)e.aux) & (aux_bits ? 7 : 15)) || e.ld_aux % (aux_bits ? 2 : 8))) return false;
     int v = pick_variant(at, bt, M, N, split_k);
     if (e.slab_bf16 && (!pk128(v) || split_k < 2 || e.kind != CG_EPI_STORE)) return false;
     if (K % (FBK * split_k)) {

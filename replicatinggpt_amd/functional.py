@@ -534,7 +534,7 @@ def _relu_bits_ok(a, w1, w2, F):
 
 
 def colsum_into(x2, out, beta):
-    ws = torch.empty(ops.colsum_workspace(x2.shape[0], x2.shape[1]) // 4 + 1, dtype=torch.float32, device=x2.device)
+    ws = torch.empty(ops.colsum_workspace(x2.shape[0], x2.shape[1]) // 4, dtype=torch.float32, device=x2.device)
     ops.colsum(x2, out, bool(beta), ws)
 
 
@@ -615,7 +615,7 @@ def layernorm_bwd(dy2, x2, w_reg, b_reg, mean, rstd, dres=None, want_lp=False, l
             # a temporary (the bias's .grad was assigned from outside) would be lost here: only the
             # consumer's own backward can hand one to autograd, so it computes these column sums itself
             gcs, bcs, fcs = None, 0.0, None
-    ws = torch.empty(ops.layernorm_bwd_workspace(rows, C) // 4 + 1, dtype=torch.float32, device=dev)
+    ws = torch.empty(ops.layernorm_bwd_workspace(rows, C) // 4, dtype=torch.float32, device=dev)
     p = float(link.p) if use_link else 0.0
     seed, rng, site = (int(link.seed) if use_link else 0), (link.rng_call if (use_link and p > 0) else None), \
         (int(link.site) if use_link else 0)
@@ -700,7 +700,7 @@ def rowdot_ok(dy2, w, o, T, D):
 def attention_bwd(qkv, B, T, H, D, o, do, lse, scale, p, seed, rng_call, site, mask=None, delta=None):
     d = H * D
     dqkv = torch.empty_like(qkv)
-    ws = torch.empty(ops.attn_bwd_workspace(B, T, H, D) // 4 + 1, dtype=torch.float32, device=qkv.device)
+    ws = torch.empty(ops.attn_bwd_workspace(B, T, H, D) // 4, dtype=torch.float32, device=qkv.device)
     if "skip_attn" in WHATIF:
         return dqkv
     ops.attn_bwd(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), o, o.stride(0), do, do.stride(0), lse, dqkv,
@@ -760,7 +760,7 @@ class EmbeddingFn(torch.autograd.Function):
         gt, bt, ft = wte_reg.grad_target()
         gp, bp, fp = wpe_reg.grad_target()
         if gt is not None or gp is not None:
-            ws = torch.empty(ops.embed_bwd_workspace(B, T, C, V) // 4 + 1, dtype=torch.float32, device=dx.device)
+            ws = torch.empty(ops.embed_bwd_workspace(B, T, C, V) // 4, dtype=torch.float32, device=dx.device)
             if bt != bp and gt is not None and gp is not None:
                 ops.embed_bwd(idx, dx.contiguous(), gt, None, bool(bt), ws)
                 ops.embed_bwd(idx, dx.contiguous(), None, gp[:T], bool(bp), ws)
