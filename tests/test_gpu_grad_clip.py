@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from numerics import fma32 as _fma32    # the exactly rounded float32 fma of the AdamW restatements
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -97,19 +99,6 @@ def test_grad_norm_inf_and_nan():
     assert np.isnan(norm)
 
 
-def _fma32(a, b, c):
-    """Exactly rounded float32 fma(a, b, c) on numpy arrays (float64 sum, fixed up with exact
-    rationals wherever that sum is not already a float32)."""
-    from fractions import Fraction
-    a, b, c = (np.broadcast_to(np.asarray(x, np.float32), np.shape(c)).astype(np.float32) for x in (a, b, c))
-    r = a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)
-    out = r.astype(np.float32)
-    for i in np.nonzero(r != out.astype(np.float64))[0]:
-        ex = Fraction(float(a[i])) * Fraction(float(b[i])) + Fraction(float(c[i]))
-        lo = np.float32(float(ex))
-        cands = [np.nextafter(lo, np.float32(-np.inf)), lo, np.nextafter(lo, np.float32(np.inf))]
-        out[i] = min(cands, key=lambda x: (abs(Fraction(float(x)) - ex), int(np.float32(x).view(np.uint32)) & 1))
-    return out
 
 
 def test_adamw_dyn_bitwise():
