@@ -547,16 +547,33 @@ def embed_plain(idx, dx, V):
 
 
 # ---- AdamW: csrc/adamw.h adam_one / adam_scalars restated rounding by rounding in numpy -------------------
-def fma32(a, b, c):
+def fma32(a, b, c, every=False):
     """Exactly rounded float32 fma(a, b, c) on numpy arrays (float64 sum, fixed up with exact
-    rationals wherever that sum is not already a float32)."""
+    rationals where rounding that sum to float32 could differ from rounding the exact value).
+
+    The product of two float32 is exact in float64, so r = fl64(a b + c) is the one inexact step, and
+    rounding to float64 is monotonic: the exact value and r lie on the same side of every float32
+    midpoint (all of them are float64 numbers) unless r IS such a midpoint.  Only there, and only if
+    the float64 sum was inexact (its TwoSum error is not 0), can float32(r) be the wrong neighbour --
+    a handful of elements in 10^9, so whole flat parameter buffers are affordable (tests/trajectory.py).
+    every=True fixes up every element whose r is not a float32, the slow original selection
+    (test_cpu_trajectory.py holds the two equal)."""
     from fractions import Fraction
     f = np.float32
     a, b, c = (np.broadcast_to(np.asarray(x, f), np.shape(c)).astype(f) for x in (a, b, c))
     with np.errstate(all="ignore"):
-        r = a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)
+        p, c64 = a.astype(np.float64) * b.astype(np.float64), c.astype(np.float64)
+        r = p + c64
         out = r.astype(f)
-    for i in np.nonzero(np.isfinite(r) & np.isfinite(out) & (r != out.astype(np.float64)))[0]:
+        sel = np.isfinite(r) & np.isfinite(out) & (r != out.astype(np.float64))
+        if not every:
+            bb = r - p
+            err = (p - (r - bb)) + (c64 - bb)          # TwoSum: p + c64 == r + err exactly
+            toward = np.where(r > out.astype(np.float64), f(np.inf), f(-np.inf)).astype(f)
+            other = np.nextafter(out, toward).astype(np.float64)
+            tie = np.abs(r - out.astype(np.float64)) == np.abs(other - r)
+            sel &= tie & ~(err == 0)                   # (a NaN err keeps the element: fixed up exactly)
+    for i in np.nonzero(sel)[0]:
         ex = Fraction(float(a[i])) * Fraction(float(b[i])) + Fraction(float(c[i]))
         lo = f(float(ex))
         cands = [np.nextafter(lo, f(-np.inf)), lo, np.nextafter(lo, f(np.inf))]
