@@ -149,6 +149,13 @@ int cg_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, void* stream);
 int cg_gather_batch(const void* data, int data_is_u8, const int64_t* ix, int64_t* x, int64_t* y,
                     int64_t B, int64_t T, void* stream);
 
+/* (prompt, completion) rows for fine-tuning.  table int64 [N, T+1]: row n holds tlen[n] <= T+1 packed
+   tokens, the first plen[n] of them the prompt (1 <= plen < tlen); ix[B] row indices in [0, N).
+   x[b,j] = table[ix[b], j] for j < tlen-1, else pad_token;
+   y[b,j] = table[ix[b], j+1] when plen <= j+1 < tlen, else ignore_index.  x, y int64 [B, T] dense. */
+int cg_gather_pairs(const int64_t* table, const int64_t* plen, const int64_t* tlen, const int64_t* ix, int64_t* x,
+                    int64_t* y, int64_t B, int64_t T, int64_t pad_token, int64_t ignore_index, void* stream);
+
 /* ---- embeddings (GPT1.py:179-181) ------------------------------------------------------ */
 /* x[b,t,:] = wte[idx[b,t],:] + wpe[t,:]  (fp32)                                          */
 int cg_embed_fwd(const int64_t* idx, const float* wte, const float* wpe, float* x, int64_t B, int64_t T,
@@ -383,6 +390,35 @@ int cg_head_bwd(const float* logits, const float* lse, const int64_t* targets, c
 int cg_head_bwd_ex(const float* logits, const float* lse, const int64_t* targets, const float* g_loss, float g_mult,
                    const float* g_logits, void* dl, int64_t ld_dl, float* db, int db_accumulate, void* workspace,
                    int64_t M, int64_t V, int flags, void* stream);
+
+/* ---- masked cross entropy (F.cross_entropy's ignore_index; DESIGN.md "Masked cross entropy") ----
+   Every operand is dense.  A row whose target equals ignore_index adds nothing to the loss and has a
+   zero gradient (a literal 0: NaN or inf in its logits cannot leak); the mean is over the other
+   ("valid") rows.  The normaliser lives on the device: float norm[2] = {valid rows, 1 / valid rows},
+   written by the forward (cg_head_fwd_masked / cg_ce_mean_masked) and read by the backward, so a
+   captured graph follows the batch.  No valid row: norm = {0, inf}, the loss is NaN (torch's 0 / 0)
+   and every gradient 0.  A target that is neither ignore_index nor in [0, V) makes the loss NaN.
+   With no row ignored the results have the bits of the unmasked entry points.
+   Fused bf16 head: the shapes of cg_head_fwd / cg_head_bwd_ex; logits and lse are written for every
+   row; workspace cg_head_masked_workspace(M, V) bytes (both directions); dl bf16 [M, KP] dense.     */
+int64_t cg_head_masked_workspace(int64_t M, int64_t V);
+int cg_head_fwd_masked(const void* a, const void* wpad, int64_t wpad_rows, const float* bias, const int64_t* targets,
+                       int64_t ignore_index, float* logits, float* lse, float* loss, float* norm, void* workspace,
+                       int64_t M, int64_t C, int64_t V, void* stream);
+int cg_head_bwd_masked(const float* logits, const float* lse, const int64_t* targets, int64_t ignore_index,
+                       const float* g_loss, const float* norm, const float* g_logits, void* dl, int64_t KP, float* db,
+                       int db_accumulate, void* workspace, int64_t M, int64_t V, int flags, void* stream);
+/* fp32 path: logits fp32 [rows, V] dense.  fwd: loss_rows[r] = lse_r - logit[r, tgt_r], 0 on ignored
+   rows.  mean: *loss = sum(loss_rows) * norm[1] and norm, one launch, fixed order (workspace
+   cg_ce_mean_masked_workspace(rows) bytes).  bwd: dlogits = (*g) norm[1] (softmax - onehot).          */
+int cg_ce_fwd_masked(const float* logits, int64_t rows, int64_t V, const int64_t* targets, int64_t ignore_index,
+                     float* loss_rows, float* lse, void* stream);
+int64_t cg_ce_mean_masked_workspace(int64_t rows);
+int cg_ce_mean_masked(const float* loss_rows, const int64_t* targets, int64_t rows, int64_t ignore_index, float* loss,
+                      float* norm, void* workspace, void* stream);
+int cg_ce_bwd_masked(const float* logits, int64_t rows, int64_t V, const int64_t* targets, int64_t ignore_index,
+                     const float* lse, const float* g, const float* norm, float* dlogits,
+                     void* dst_lp /* optional bf16 copy */, void* stream);
 
 /* ---- batched decode for generate() (GPT1.py:196-212; replicatinggpt_amd/decode.py) ----------
    len_dev: device int64 = current sequence length (tokens in idx rows, row stride ld).          */

@@ -46,6 +46,7 @@ _SIGS = {
     "cg_sum_f32": (c_int, [P, c_i64, c_flt, P, P, P]),
     "cg_cast_f32_bf16": (c_int, [P, P, c_i64, P]),
     "cg_gather_batch": (c_int, [P, c_int, P, P, P, c_i64, c_i64, P]),
+    "cg_gather_pairs": (c_int, [P, P, P, P, P, P, c_i64, c_i64, c_i64, c_i64, P]),
     "cg_embed_fwd": (c_int, [P, P, P, P, c_i64, c_i64, c_i64, c_i64, P]),
     "cg_embed_bwd_workspace": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     "cg_embed_bwd": (c_int, [P, P, P, P, c_i64, c_i64, c_i64, c_i64, c_int, P, P]),
@@ -100,6 +101,13 @@ _SIGS = {
     "cg_head_fwd": (c_int, [P, P, c_i64, P, P, P, P, P, P, c_i64, c_i64, c_i64, P]),
     "cg_head_bwd": (c_int, [P, P, P, P, c_flt, P, P, c_i64, P, c_int, P, c_i64, c_i64, P]),
     "cg_head_bwd_ex": (c_int, [P, P, P, P, c_flt, P, P, c_i64, P, c_int, P, c_i64, c_i64, c_int, P]),
+    "cg_head_masked_workspace": (c_i64, [c_i64, c_i64]),
+    "cg_head_fwd_masked": (c_int, [P, P, c_i64, P, P, c_i64, P, P, P, P, P, c_i64, c_i64, c_i64, P]),
+    "cg_head_bwd_masked": (c_int, [P, P, P, c_i64, P, P, P, P, c_i64, P, c_int, P, c_i64, c_i64, c_int, P]),
+    "cg_ce_fwd_masked": (c_int, [P, c_i64, c_i64, P, c_i64, P, P, P]),
+    "cg_ce_mean_masked_workspace": (c_i64, [c_i64]),
+    "cg_ce_mean_masked": (c_int, [P, P, c_i64, c_i64, P, P, P, P]),
+    "cg_ce_bwd_masked": (c_int, [P, c_i64, c_i64, P, c_i64, P, P, P, P, P, P]),
     "cg_decode_window": (c_int, [P, c_i64, c_i64, c_i64, P, P, P]),
     "cg_decode_embed": (c_int, [P, c_i64, P, P, c_i64, P, P, c_i64, P]),
     "cg_decode_kv_append": (c_int, [P, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, P, P, P, P]),

@@ -200,6 +200,33 @@ extern "C" int cg_gather_batch(const void* data, int data_is_u8, const int64_t* 
     return CG_OK;
 }
 
+// (prompt, completion) rows for fine-tuning: row ix[b] of the packed table, padded past its length,
+// with the targets of the prompt and of the padding set to ignore
+__global__ void k_gather_pairs(const int64_t* __restrict__ table, const int64_t* __restrict__ plen,
+                               const int64_t* __restrict__ tlen, const int64_t* __restrict__ ix,
+                               int64_t* __restrict__ x, int64_t* __restrict__ y, int64_t T, int64_t pad,
+                               int64_t ignore) {
+    const int64_t b = blockIdx.y;
+    const int64_t r = ix[b];
+    const int64_t pl = plen[r], tl = tlen[r];
+    const int64_t* row = table + r * (T + 1);
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (int64_t)gridDim.x * blockDim.x) {
+        x[b * T + t] = t < tl - 1 ? row[t] : pad;
+        y[b * T + t] = (pl <= t + 1 && t + 1 < tl) ? row[t + 1] : ignore;
+    }
+}
+
+extern "C" int cg_gather_pairs(const int64_t* table, const int64_t* plen, const int64_t* tlen, const int64_t* ix,
+                               int64_t* x, int64_t* y, int64_t B, int64_t T, int64_t pad_token, int64_t ignore_index,
+                               void* stream) {
+    CG_REQUIRE(B > 0 && T > 0 && B < 65536, "cg_gather_pairs: bad shape");
+    CG_REQUIRE(table && plen && tlen && ix && x && y, "cg_gather_pairs: null operand");
+    dim3 grid(ceil_div(T, 256), (unsigned)B);
+    k_gather_pairs<<<grid, 256, 0, (hipStream_t)stream>>>(table, plen, tlen, ix, x, y, T, pad_token, ignore_index);
+    CG_LAUNCH_CHECK("cg_gather_pairs");
+    return CG_OK;
+}
+
 extern "C" int cg_timing_event_create(void** event) {
     CG_REQUIRE(event, "cg_timing_event_create: null");
     hipEvent_t e = nullptr;

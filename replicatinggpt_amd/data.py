@@ -11,6 +11,10 @@
   kernel instead of 2*B Python slices + stack + H2D copy.  With data parallelism every rank draws the
   same global ``B*W`` offsets and keeps its own slice (one draw of B*W == W consecutive reference
   draws).
+* ``PairSampler`` -- fine-tuning on (prompt, completion) pairs, which GPT1.py does not have: one pair
+  per batch row, the loss taken on the completion only (targets elsewhere are ``ignore_index``, the
+  masked cross entropy of DESIGN.md §4).  Row indices are drawn like BatchSampler's offsets; the rows
+  are gathered, padded and masked on the device (cg_gather_pairs).
 """
 import os
 
@@ -116,4 +120,93 @@ class BatchSampler:
         else:
             x, y = out
         ops.gather_batch(data, ix_dev, x, y)
+        return x, y
+
+
+def pack_pairs(pairs, block_size):
+    """Pack (prompt_tokens, completion_tokens) pairs into an int64 table [N, T+1] (row = prompt +
+    completion, zero-filled past its length) with the prompt lengths ``plen`` and total lengths
+    ``tlen``.  A row longer than T+1 loses the front of its prompt; at least one prompt token stays,
+    since the first completion token is predicted from it."""
+    T = block_size
+    table = torch.zeros((len(pairs), T + 1), dtype=torch.int64)
+    plen = torch.empty(len(pairs), dtype=torch.int64)
+    tlen = torch.empty(len(pairs), dtype=torch.int64)
+    for n, (prompt, completion) in enumerate(pairs):
+        prompt, completion = list(prompt), list(completion)
+        if not prompt or not completion:
+            raise ValueError(f"pair {n}: the prompt and the completion must both be non-empty")
+        if len(completion) > T:
+            raise ValueError(f"pair {n}: a completion of {len(completion)} tokens does not fit block_size {T} "
+                             "(one prompt token must precede it)")
+        over = len(prompt) + len(completion) - (T + 1)
+        if over > 0:
+            prompt = prompt[over:]
+        row = prompt + completion
+        table[n, :len(row)] = torch.tensor(row, dtype=torch.int64)
+        plen[n], tlen[n] = len(prompt), len(row)
+    return table, plen, tlen
+
+
+class PairSampler:
+    """get_batch over (prompt, completion) pairs: x[b] = the packed row up to its last input token,
+    ``pad_token`` after it; y[b, j] = the next token where that token belongs to the completion,
+    ``ignore_index`` (-100, F.cross_entropy's default) elsewhere.  90/10 train/val split of the rows,
+    as TokenStream's.  Every rank draws the same global B*W row indices on the CPU generator and
+    keeps its own slice, exactly as BatchSampler does."""
+
+    ignore_index = -100
+
+    def __init__(self, pairs, block_size, batch_size, world_size=1, rank=0, generator=None, pad_token=0,
+                 device=None):
+        self.T = block_size
+        self.B = batch_size
+        self.W = world_size
+        self.rank = rank
+        self.generator = generator
+        self.pad_token = int(pad_token)
+        self.table_cpu, self.plen_cpu, self.tlen_cpu = pack_pairs(pairs, block_size)
+        self.n = int(0.9 * len(pairs))      # rows [0, n) train, [n, N) val
+        self.device = None
+        self.table_dev = self.plen_dev = self.tlen_dev = None
+        self._ring = None
+        self._ring_i = 0
+        if device is not None:
+            self.to(device)
+
+    def to(self, device):
+        self.device = torch.device(device)
+        self.table_dev = self.table_cpu.to(self.device)
+        self.plen_dev = self.plen_cpu.to(self.device)
+        self.tlen_dev = self.tlen_cpu.to(self.device)
+        return self
+
+    _staging = BatchSampler._staging
+
+    def draw_ix(self, split):
+        """Global draw of B*W row indices of ``split`` on the CPU generator (rank-sliced)."""
+        lo, n = (0, self.n) if split == "train" else (self.n, len(self.table_cpu) - self.n)
+        if n <= 0:
+            raise ValueError(f"PairSampler: the {split} split is empty ({len(self.table_cpu)} pairs, 90/10 split)")
+        ix = torch.randint(n, (self.B * self.W,), generator=self.generator)
+        return ix[self.rank * self.B:(self.rank + 1) * self.B] + lo
+
+    def get_batch(self, split, out=None):
+        ix = self.draw_ix(split)
+        if self.table_dev is None:
+            self.to("cuda")
+        dev = self.device
+        i, buf = self._staging(dev)
+        buf.copy_(ix)
+        ix_dev = buf.to(dev, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._ring[i] = (buf, ev)
+        if out is None:
+            x = torch.empty((self.B, self.T), dtype=torch.int64, device=dev)
+            y = torch.empty((self.B, self.T), dtype=torch.int64, device=dev)
+        else:
+            x, y = out
+        ops.gather_pairs(self.table_dev, self.plen_dev, self.tlen_dev, ix_dev, x, y, self.pad_token,
+                         self.ignore_index)
         return x, y

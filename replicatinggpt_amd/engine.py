@@ -16,6 +16,12 @@ of the backward with only eager collectives (no collective is captured in a grap
 here depends on RCCL graph capture).  The optimizer is a final graph replayed after the
 collectives have been waited on.
 
+A sampler with an ``ignore_index`` attribute (data.PairSampler) trains on masked targets: the loss
+is the mean over the batch's valid tokens, with the normaliser computed and read on the device, so
+a replayed graph follows each batch's count.  Data parallel training keeps torch-DDP semantics:
+each rank's loss is the mean over its OWN valid tokens and the gradients are averaged across ranks
+(not weighted by the ranks' token counts).
+
 A learning-rate schedule (``lr_schedule``: iteration -> lr) needs an optimizer in dynamic mode
 (optim.AdamW(dynamic_lr=True) or max_grad_norm): its update reads the learning rate from the device
 when it runs, so ``step`` writes the iteration's value before the replay.  The gradient-norm and
@@ -94,6 +100,9 @@ class TrainStep:
                              "(AdamW(dynamic_lr=True) or max_grad_norm=...): a captured step keeps a by-value "
                              "learning rate")
         self.lr_schedule = lr_schedule
+        # data.PairSampler marks the targets outside the completion with its ignore_index
+        ignore = getattr(sampler, "ignore_index", None)
+        self._loss_kw = {} if ignore is None else {"ignore_index": ignore}
         self.it = 0   # the iteration the next step() takes (settable: a resumed run continues its schedule)
         dev = model.flat.master.device
         B, T = sampler.B, sampler.T
@@ -113,7 +122,7 @@ class TrainStep:
 
     # -- eager ----------------------------------------------------------------------------
     def _fwd_bwd(self):
-        _, loss = self.model(self.x, self.y)           # GPT1.py:230
+        _, loss = self.model(self.x, self.y, **self._loss_kw)   # GPT1.py:230
         self.opt.zero_grad(set_to_none=True)           # GPT1.py:231
         # one rank: the weight matrices' AdamW beside the backward's GEMMs
         early = self.reducer is None and Fn.EARLY.begin(self.opt)
@@ -156,7 +165,7 @@ class TrainStep:
             return hook
         hooks = [self.model.blocks[j].register_forward_pre_hook(grab(j)) for j in self.cuts]
         try:
-            _, loss = self.model(self.x, self.y)
+            _, loss = self.model(self.x, self.y, **self._loss_kw)
         finally:
             for h in hooks:
                 h.remove()
@@ -320,7 +329,8 @@ class Evaluator:
         self.out = None
 
     def _forward(self):
-        _, loss = self.model(self.x, self.y)
+        ignore = getattr(self.sampler, "ignore_index", None)   # data.PairSampler: masked targets
+        _, loss = self.model(self.x, self.y, **({} if ignore is None else {"ignore_index": ignore}))
         return loss
 
     @torch.no_grad()

@@ -1020,10 +1020,21 @@ class FFNSublayerFn(torch.autograd.Function):
 
 
 class HeadLossFn(torch.autograd.Function):
-    """ln_f -> lm_head -> (optional) mean cross entropy   (GPT1.py:183-192)."""
+    """ln_f -> lm_head -> (optional) mean cross entropy   (GPT1.py:183-192).
+
+    ``apply(x, targets, act, ln_w, ln_b, lm_w, lm_b, *params[, ignore_index])``: an int after the
+    parameter tensors is F.cross_entropy's ``ignore_index`` -- targets equal to it add nothing to the
+    loss or the gradients and the mean is over the others (the masked entry points of csrc/head.hip and
+    csrc/ce_adamw.hip; the normaliser stays on the device, saved for the backward).  Without it (or
+    with None) the unmasked kernels run, as they always did."""
 
     @staticmethod
     def forward(ctx, x, targets, act, ln_w, ln_b, lm_w, lm_b, *params):
+        ignore_index = None
+        if params and not isinstance(params[-1], torch.Tensor):
+            ignore_index, params = params[-1], params[:-1]
+            ctx.ignore_slot = True
+        ctx.ignore_index = None if (ignore_index is None or targets is None) else int(ignore_index)
         B, T, C = x.shape
         M = B * T
         x2 = x.reshape(M, C)
@@ -1045,8 +1056,17 @@ class HeadLossFn(torch.autograd.Function):
             return logits.view(B, T, V)
         t1 = targets.reshape(M)
         loss_rows = torch.empty(M, dtype=torch.float32, device=x.device)
-        ops.ce_fwd(logits, t1, loss_rows, lse)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
+        if ctx.ignore_index is not None:
+            t1 = t1.contiguous()
+            ops.ce_fwd_masked(logits, t1, ctx.ignore_index, loss_rows, lse)
+            norm = torch.empty(2, dtype=torch.float32, device=x.device)
+            ws = torch.empty(ops.ce_mean_masked_workspace(M) // 4, dtype=torch.float32, device=x.device)
+            ops.ce_mean_masked(loss_rows, t1, ctx.ignore_index, loss, norm, ws)
+            ctx.save_for_backward(x2, a, mean, rstd, logits, lse, t1, norm)
+            ctx.has_targets = True
+            return logits, loss
+        ops.ce_fwd(logits, t1, loss_rows, lse)
         ws = torch.empty(1024, dtype=torch.float32, device=x.device)
         ops.sum_scaled(loss_rows, 1.0 / M, loss, ws)
         ctx.save_for_backward(x2, a, mean, rstd, logits, lse, t1)
@@ -1059,19 +1079,28 @@ class HeadLossFn(torch.autograd.Function):
         B, T, C = ctx.shape
         act = ctx.act
         M = B * T
+        norm = None
         if ctx.has_targets:
-            x2, a, mean, rstd, logits, lse, t1 = ctx.saved_tensors
+            if ctx.ignore_index is not None:
+                x2, a, mean, rstd, logits, lse, t1, norm = ctx.saved_tensors
+            else:
+                x2, a, mean, rstd, logits, lse, t1 = ctx.saved_tensors
             g_logits, g_loss = grads
         else:
             x2, a, mean, rstd, logits, lse = ctx.saved_tensors
             g_logits, g_loss = grads[0], None
         V = logits.shape[-1]
+        tail = (None,) if getattr(ctx, "ignore_slot", False) else ()   # the ignore_index argument's slot
         if ctx.fused:
             return HeadLossFn._fused_backward(ctx, x2, a, mean, rstd, logits, lse, t1 if ctx.has_targets else None,
-                                              g_logits, g_loss)
+                                              g_logits, g_loss, norm) + tail
         dl = torch.empty((M, V), dtype=torch.float32, device=x2.device)
         if g_loss is not None:
-            ops.ce_bwd(logits, t1, lse, g_loss.reshape(1).float().contiguous(), 1.0 / M, dl, None)
+            if norm is not None:
+                ops.ce_bwd_masked(logits, t1, ctx.ignore_index, lse, g_loss.reshape(1).float().contiguous(), norm, dl,
+                                  None)
+            else:
+                ops.ce_bwd(logits, t1, lse, g_loss.reshape(1).float().contiguous(), 1.0 / M, dl, None)
             if g_logits is not None:
                 dl.add_(g_logits.reshape(M, V))
         else:
@@ -1086,7 +1115,7 @@ class HeadLossFn(torch.autograd.Function):
         da = torch.empty((M, C), dtype=act, device=x2.device)
         linear_dgrad(dl_op, lm_w.operand(act), da)
         dx, _, f_ln = layernorm_bwd(da, x2, ln_w, ln_b, mean, rstd, link=ctx.in_link)
-        return (dx.view(B, T, C), None, None, None, None, None, None, *f_ln, *f_lw(), *f_lb())
+        return (dx.view(B, T, C), None, None, None, None, None, None, *f_ln, *f_lw(), *f_lb()) + tail
 
     # -- bf16 fast path: cg_head_fwd/bwd + K-padded MFMA GEMMs (csrc/head.hip) -------------
     @staticmethod
@@ -1106,6 +1135,14 @@ class HeadLossFn(torch.autograd.Function):
             return logits.view(B, T, V)
         t1 = targets.reshape(M)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
+        if ctx.ignore_index is not None:
+            t1 = t1.contiguous()
+            norm = torch.empty(2, dtype=torch.float32, device=x.device)
+            ws = torch.empty(ops.head_masked_workspace(M, V) // 4, dtype=torch.float32, device=x.device)
+            ops.head_fwd_masked(a, wpad, lm_b.master, t1, ctx.ignore_index, logits, lse, loss, norm, ws)
+            ctx.save_for_backward(x2, a, mean, rstd, logits, lse, t1, norm)
+            ctx.has_targets = True
+            return logits, loss
         ws = torch.empty(ops.head_workspace(M, V) // 4, dtype=torch.float32, device=x.device)
         ops.head_fwd(a, wpad, lm_b.master, t1, logits, lse, loss, ws)
         ctx.save_for_backward(x2, a, mean, rstd, logits, lse, t1)
@@ -1113,7 +1150,7 @@ class HeadLossFn(torch.autograd.Function):
         return logits, loss
 
     @staticmethod
-    def _fused_backward(ctx, x2, a, mean, rstd, logits, lse, t1, g_logits, g_loss):
+    def _fused_backward(ctx, x2, a, mean, rstd, logits, lse, t1, g_logits, g_loss, norm=None):
         ln_w, ln_b, lm_w, lm_b = ctx.regs
         B, T, C = ctx.shape
         M, V = logits.shape
@@ -1121,14 +1158,20 @@ class HeadLossFn(torch.autograd.Function):
         KP = wpad.shape[0]
         dl = torch.empty((M, KP), dtype=torch.bfloat16, device=x2.device)
         gb, beta_b, f_lb = lm_b.grad_target()
-        ws = torch.empty(ops.head_workspace(M, V) // 4, dtype=torch.float32, device=x2.device)
+        masked = norm is not None and g_loss is not None   # no loss gradient: dl = g_logits, nothing to mask
+        ws_bytes = ops.head_masked_workspace(M, V) if masked else ops.head_workspace(M, V)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x2.device)
         gl = None if g_logits is None else g_logits.reshape(M, V).float().contiguous()
         if g_loss is None:
             t1 = None
         # the lm_head bias gradient's column-sum reduce joins DEFER's multi-job flush when it targets the slot
         with DEFER.partials(ws) if (gb is not None and gb is lm_b.slot) else contextlib.nullcontext(False) as queued:
-            ops.head_bwd(logits, lse, t1, None if g_loss is None else g_loss.reshape(1).float().contiguous(), 1.0 / M,
-                         gl, dl, gb, bool(beta_b), ws, queued)
+            if masked:
+                ops.head_bwd_masked(logits, lse, t1, ctx.ignore_index, g_loss.reshape(1).float().contiguous(), norm, gl,
+                                    dl, gb, bool(beta_b), ws, queued)
+            else:
+                ops.head_bwd(logits, lse, t1, None if g_loss is None else g_loss.reshape(1).float().contiguous(),
+                             1.0 / M, gl, dl, gb, bool(beta_b), ws, queued)
         g, beta, f_lw = lm_w.grad_target()
         if g is not None:
             if g.data_ptr() == lm_w.slot.data_ptr():

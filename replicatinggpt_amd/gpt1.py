@@ -21,16 +21,21 @@ Deliberate differences from GPT1.py:
   (linear warm-up, cosine decay: schedule.warmup_cosine) put the optimizer in its dynamic mode
   (optim.AdamW); with none of them given the driver builds exactly the objects it built before.  A
   resumed run continues the schedule from the checkpoint's iteration;
+* ``--pairs FILE`` fine-tunes on (prompt, completion) pairs -- JSON lines ``{"prompt": ..., "completion":
+  ...}`` tokenised with the ``--input`` vocabulary -- with the loss on the completions only
+  (data.PairSampler, the masked cross entropy of DESIGN.md §4); ``--init-from model.pth`` loads a state
+  dict first, since fine-tuning starts from a trained model.  Without them nothing changes;
 * dropout masks come from charpt's Philox stream, so with Dropout > 0 the loss
   curve matches the reference's within tolerance, not bit for bit (tests/test_gpu_train.py).
 """
 import argparse
+import json
 
 import torch
 
 from . import checkpoint
 from .config import PRESETS
-from .data import DEFAULT_INPUT, BatchSampler, TokenStream
+from .data import DEFAULT_INPUT, BatchSampler, PairSampler, TokenStream
 from .engine import Evaluator, TrainStep
 from .model import BigramLanguageModel
 from .optim import AdamW
@@ -51,11 +56,33 @@ def estimate_loss(model, sampler, eval_iters, evaluator=None):
                 losses[k] = evaluator.loss(split)                             # :92-93, graph replay
             else:
                 X, Y = sampler.get_batch(split)                               # :92
-                _, loss = model(X, Y)                                         # :93
+                ignore = getattr(sampler, "ignore_index", None)               # PairSampler: masked targets
+                _, loss = model(X, Y) if ignore is None else model(X, Y, ignore_index=ignore)   # :93
                 losses[k] = loss                                              # :94 (no host sync)
         out[split] = losses.cpu().mean()                                      # :95
     model.train()                                                             # :96
     return out
+
+
+def read_pairs(path, tok):
+    """JSON lines {"prompt": str, "completion": str} -> [(prompt_tokens, completion_tokens)] in
+    ``tok``'s vocabulary; a character outside it is an error naming the line."""
+    pairs = []
+    with open(path, "r", encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            try:
+                rec = json.loads(line)
+                prompt, completion = rec["prompt"], rec["completion"]
+            except (ValueError, KeyError, TypeError) as e:
+                raise SystemExit(f"{path}:{no}: expected a JSON object with \"prompt\" and \"completion\": {e!r}")
+            for side, text in (("prompt", prompt), ("completion", completion)):
+                bad = sorted(set(c for c in text if c not in tok.stoi))
+                if bad:
+                    raise SystemExit(f"{path}:{no}: {side} has characters outside the --input vocabulary: {bad!r}")
+            pairs.append((tok.encode(prompt), tok.encode(completion)))
+    return pairs
 
 
 def parse_args(argv=None):
@@ -78,6 +105,9 @@ def parse_args(argv=None):
     ap.add_argument("--out", default="model.pth", help="state dict file (GPT1.py:240); '' to skip")
     ap.add_argument("--save-checkpoint", default=None, help="also write a resumable training checkpoint")
     ap.add_argument("--resume", default=None, help="continue from a --save-checkpoint file")
+    ap.add_argument("--pairs", default=None, help="fine-tune on JSON lines {\"prompt\", \"completion\"}: loss on the "
+                    "completions only")
+    ap.add_argument("--init-from", default=None, help="load this state dict (a --out file) before training")
     ap.add_argument("--no-graph", action="store_true", help="eager steps instead of hipGraph replay")
     return ap.parse_args(argv)
 
@@ -96,6 +126,8 @@ def main(argv=None):
     cfg = cfg.with_(vocab_size=tok.vocab_size)
     model = BigramLanguageModel(cfg)                                          # GPT1.py:215
     m = model.to(device)                                                      # GPT1.py:216
+    if a.init_from:
+        checkpoint.load_model(m, a.init_from)
     lr = a.lr if a.lr is not None else cfg.optimizer_lr
     schedule = None
     if a.warmup_iters is not None or a.lr_decay_iters is not None or a.min_lr is not None:
@@ -109,7 +141,10 @@ def main(argv=None):
         optimizer = AdamW(m.parameters(), lr=lr)                              # GPT1.py:218
     else:
         optimizer = AdamW(m.parameters(), lr=lr, max_grad_norm=a.grad_clip, dynamic_lr=True)
-    sampler = BatchSampler(stream, cfg.block_size, cfg.batch_size)           # GPT1.py:75-83
+    if a.pairs:
+        sampler = PairSampler(read_pairs(a.pairs, tok), cfg.block_size, cfg.batch_size, device=device)
+    else:
+        sampler = BatchSampler(stream, cfg.block_size, cfg.batch_size)       # GPT1.py:75-83
     start = checkpoint.load_checkpoint(a.resume, m, optimizer) if a.resume else 0
     if schedule is None:
         step = TrainStep(m, optimizer, sampler, use_graph=not a.no_graph)

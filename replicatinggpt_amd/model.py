@@ -454,7 +454,11 @@ class BigramLanguageModel(nn.Module):
             st.refresh_shadow()
 
     # -- forward (GPT1.py:176-194) -----------------------------------------------------
-    def forward(self, idx, targets=None):
+    def forward(self, idx, targets=None, ignore_index=None):
+        """``ignore_index`` (F.cross_entropy's; data.PairSampler uses -100): targets equal to it are
+        left out of the loss and its gradients, the mean is over the others.  It is a launch argument
+        of the masked loss kernels -- the targets are never inspected on the host.  None (default): the
+        unmasked loss of GPT1.py:192."""
         _require_hip(idx)
         cfg = self.config
         idx = idx.contiguous()          # generate() passes a column slice idx[:, -block_size:]
@@ -480,8 +484,9 @@ class BigramLanguageModel(nn.Module):
             x = Fn.EmbeddingFn.apply(idx, wte, wpe, *wte.params, *wpe.params)
             x = self.blocks(x)
             lw, lb, hw, hb = R["lnf_w"], R["lnf_b"], R["lm_w"], R["lm_b"]
+            masked = () if (ignore_index is None or targets is None) else (int(ignore_index),)
             out = Fn.HeadLossFn.apply(x, targets, act, lw, lb, hw, hb, *lw.params, *lb.params, *hw.params,
-                                      *hb.params)
+                                      *hb.params, *masked)
         finally:
             self._fwd_rng = None
             self._premasks = None

@@ -65,6 +65,17 @@ def gather_batch(data: Tensor, ix: Tensor, x: Tensor, y: Tensor) -> None:
                                      T, _s(x)), "gather_batch")
 
 
+@_op("gather_pairs", ("x", "y"))
+def gather_pairs(table: Tensor, plen: Tensor, tlen: Tensor, ix: Tensor, x: Tensor, y: Tensor, pad_token: int,
+                 ignore_index: int) -> None:
+    """table int64 [N, T+1] packed (prompt + completion) rows; see cg_gather_pairs."""
+    B, T = x.shape
+    if table.shape[1] != T + 1 or not (table.is_contiguous() and x.is_contiguous() and y.is_contiguous()):
+        raise ValueError(f"gather_pairs: table must be dense [N, T+1] (T={T}, table {tuple(table.shape)}), x and y dense")
+    L.check(L.load().cg_gather_pairs(L.ptr(table), L.ptr(plen), L.ptr(tlen), L.ptr(ix), L.ptr(x), L.ptr(y), B, T,
+                                     pad_token, ignore_index, _s(x)), "gather_pairs")
+
+
 # ---------------------------------------------------------------------------------------
 @_op("embed_fwd", ("x",))
 def embed_fwd(idx: Tensor, wte: Tensor, wpe: Tensor, x: Tensor) -> None:
@@ -465,6 +476,73 @@ def head_bwd(logits: Tensor, lse: Tensor, targets: Optional[Tensor], g_loss: Opt
     L.check(L.load().cg_head_bwd_ex(L.ptr(logits), L.ptr(lse), L.ptr(targets), L.ptr(g_loss), g_mult,
                                     L.ptr(g_logits), L.ptr(dl), dl.stride(0), L.ptr(db), int(db_accumulate), L.ptr(ws),
                                     M, V, L.DEFER if defer else 0, _s(logits)), "head_bwd")
+
+
+# masked cross entropy (ignore_index): dense operands, the normaliser norm[2] on the device
+def _dense(name, **tensors):
+    for k, t in tensors.items():
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name}: {k} must be dense (strides {tuple(t.stride())}); the masked entry points take "
+                             "no row stride")
+
+
+def head_masked_workspace(M: int, V: int) -> int:
+    return int(L.load().cg_head_masked_workspace(M, V))
+
+
+def ce_mean_masked_workspace(rows: int) -> int:
+    return int(L.load().cg_ce_mean_masked_workspace(rows))
+
+
+@_op("head_fwd_masked", ("logits", "lse", "loss", "norm", "ws"))
+def head_fwd_masked(a: Tensor, wpad: Tensor, bias: Tensor, targets: Tensor, ignore_index: int, logits: Tensor,
+                    lse: Tensor, loss: Tensor, norm: Tensor, ws: Tensor) -> None:
+    M, C = a.shape
+    V = logits.shape[-1]
+    _dense("head_fwd_masked", a=a, wpad=wpad, targets=targets, logits=logits, lse=lse)
+    L.check(L.load().cg_head_fwd_masked(L.ptr(a), L.ptr(wpad), wpad.shape[0], L.ptr(bias), L.ptr(targets),
+                                        ignore_index, L.ptr(logits), L.ptr(lse), L.ptr(loss), L.ptr(norm), L.ptr(ws),
+                                        M, C, V, _s(a)), "head_fwd_masked")
+
+
+@_op("head_bwd_masked", ("dl", "db", "ws"))
+def head_bwd_masked(logits: Tensor, lse: Tensor, targets: Tensor, ignore_index: int, g_loss: Tensor, norm: Tensor,
+                    g_logits: Optional[Tensor], dl: Tensor, db: Optional[Tensor], db_accumulate: bool, ws: Tensor,
+                    defer: bool = False) -> None:
+    """dl: dense bf16 [M, KP].  defer: the db column-sum reduce is queued on the stream's deferral queue."""
+    M, V = logits.shape
+    _dense("head_bwd_masked", logits=logits, lse=lse, targets=targets, g_logits=g_logits, dl=dl)
+    L.check(L.load().cg_head_bwd_masked(L.ptr(logits), L.ptr(lse), L.ptr(targets), ignore_index, L.ptr(g_loss),
+                                        L.ptr(norm), L.ptr(g_logits), L.ptr(dl), dl.shape[1], L.ptr(db),
+                                        int(db_accumulate), L.ptr(ws), M, V, L.DEFER if defer else 0, _s(logits)),
+            "head_bwd_masked")
+
+
+@_op("ce_fwd_masked", ("loss_rows", "lse"))
+def ce_fwd_masked(logits: Tensor, targets: Tensor, ignore_index: int, loss_rows: Tensor, lse: Tensor) -> None:
+    V = logits.shape[-1]
+    rows = logits.numel() // V
+    _dense("ce_fwd_masked", logits=logits, targets=targets)
+    L.check(L.load().cg_ce_fwd_masked(L.ptr(logits), rows, V, L.ptr(targets), ignore_index, L.ptr(loss_rows),
+                                      L.ptr(lse), _s(logits)), "ce_fwd_masked")
+
+
+@_op("ce_mean_masked", ("loss", "norm", "ws"))
+def ce_mean_masked(loss_rows: Tensor, targets: Tensor, ignore_index: int, loss: Tensor, norm: Tensor,
+                   ws: Tensor) -> None:
+    _dense("ce_mean_masked", loss_rows=loss_rows, targets=targets)
+    L.check(L.load().cg_ce_mean_masked(L.ptr(loss_rows), L.ptr(targets), loss_rows.numel(), ignore_index,
+                                       L.ptr(loss), L.ptr(norm), L.ptr(ws), _s(loss_rows)), "ce_mean_masked")
+
+
+@_op("ce_bwd_masked", ("dlogits", "dlogits_lp"))
+def ce_bwd_masked(logits: Tensor, targets: Tensor, ignore_index: int, lse: Tensor, g: Tensor, norm: Tensor,
+                  dlogits: Optional[Tensor], dlogits_lp: Optional[Tensor]) -> None:
+    V = logits.shape[-1]
+    rows = logits.numel() // V
+    _dense("ce_bwd_masked", logits=logits, targets=targets, dlogits=dlogits, dlogits_lp=dlogits_lp)
+    L.check(L.load().cg_ce_bwd_masked(L.ptr(logits), rows, V, L.ptr(targets), ignore_index, L.ptr(lse), L.ptr(g),
+                                      L.ptr(norm), L.ptr(dlogits), L.ptr(dlogits_lp), _s(logits)), "ce_bwd_masked")
 
 
 # ---------------------------------------------------------------------------------------
