@@ -114,10 +114,15 @@ const char* cg_last_error_string(void);
 int cg_version(void);
 /* process-wide A/B and test knobs (kernel / schedule selection, never a call's numerics): e.g.
    "gemm_variant" 0 = automatic, 2 = register-staged, 9 = persistent 128x128, 24 = 8-wave 256x256,
-   97 / 98 = fp32 small-M chunked kernel / 128x64 kernel only, 99 = generic; "decode_attn_rows",
+   31 = the weight-stationary kernel for K <= 384 (whatever it takes, the rest as 2), 97 / 98 = fp32
+   small-M chunked kernel / 128x64 kernel only, 99 = generic; "gemm_ws" 0 / 1 = the automatic use of
+   the weight-stationary kernel off / on (2, 3, 4: one product only, for A/B); "decode_attn_rows",
    "red_side", "adam_per_launch", "gemm_n96", "ln_nt", ... (gemm.hip cg_set_tuning).
    Set them before the calls they affect, from one thread.                                       */
 int cg_set_tuning(const char* key, int value);
+/* launches cg_gemm has run through the weight-stationary kernel (gemm_ws.hip) in this process: for
+   tests and A/B tools that must know which kernel served a call                                  */
+int64_t cg_gemm_ws_launches(void);
 int cg_device_info(int* n_cu, int* arch_major, int* arch_minor);
 /* measurement (bench.py's in-step roofline): a timing event recorded on `stream` -- inside a
    hipGraph capture as an EXTERNAL event-record node (hipEventRecordExternal), so that each replay

@@ -247,6 +247,13 @@ bool gemm_wgrad_group_ok(int64_t M, int64_t N, int64_t K, const void* A, int64_t
 bool fast_gemm_launch(int at, int bt, int64_t M, int64_t N, int64_t K, const bf16_t* A, int64_t lda, const bf16_t* B,
                       int64_t ldb, void* C, int c_dtype, int64_t ldc, const EpiArgs& e, int split_k, float* ws,
                       hipStream_t st) {
+    // the weight-stationary kernel (gemm_ws.hip; 64-row tiles, so asked first): forced by gemm_variant 31,
+    // else for the K <= 384 wide-N products the 128x128 persistent kernel would otherwise run
+    if (g_gemm_variant == 31 ||
+        (g_gemm_variant == 0 && ws_gemm_auto(M, N, e.kind) && fast_shape_ok(M, N, K, lda, ldb, ldc, split_k) &&
+         pick_variant(at, bt, M, N, split_k) == 9)) {
+        if (ws_gemm_launch(at, bt, M, N, K, A, lda, B, ldb, C, c_dtype, ldc, e, split_k, st)) return true;
+    }
     if (!fast_shape_ok(M, N, K, lda, ldb, ldc, split_k)) return false;
     if ((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C)) & 15) return false;
     if (e.bias && (((uintptr_t)e.bias) & 15)) return false;

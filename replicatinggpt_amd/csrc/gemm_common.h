@@ -324,6 +324,15 @@ bool pk_gemm_launch(int variant, int at, int bt, int64_t M, int64_t N, int64_t K
                     const bf16_t* B, int64_t ldb, void* C, int c_dtype, int64_t ldc, const EpiArgs& e, int split_k,
                     float* ws, hipStream_t st);
 
+// the weight-stationary kernel for K <= 384 (gemm_ws.hip; gemm_variant 31, or automatically for the shapes
+// ws_gemm_auto names while cg_set_tuning("gemm_ws") is on): bf16 output, split 1, beta 0, STORE / BIAS_RELU
+// (+ keep bits) / RELU_BWD (keep bits, + column partials); false = not launched.  Takes no deferred work.
+extern int g_gemm_ws;
+bool ws_gemm_auto(int64_t M, int64_t N, int kind);
+bool ws_gemm_launch(int at, int bt, int64_t M, int64_t N, int64_t K, const bf16_t* A, int64_t lda, const bf16_t* B,
+                    int64_t ldb, void* C, int c_dtype, int64_t ldc, const EpiArgs& e, int split_k, hipStream_t st);
+long long ws_gemm_launches();
+
 // One problem of a grouped split-K weight-gradient launch (cg_gemm_wgrad_group; gemm_pk_group.hip):
 // slabs[s][M][N] = sum over split s's K-tiles of A[k][m] B[k][n].  The caller fills everything but
 // item0 and gm (pk_group_launch's).

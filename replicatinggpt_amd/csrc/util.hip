@@ -302,6 +302,7 @@ const Knob KNOBS[] = {
     {"gemm_group_p8", &g_gemm_group_p8, 0, 255},   // gemm.hip: gemm_tile.h tile_rc row panels per group (0/1: row-major)
     {"gemm_group_pk", &g_gemm_group_pk, 0, 255},   // gemm.hip: the same for k_gemm_pk
     {"gemm_n96", &g_gemm_n96, ANY_LO, ANY_HI},     // gemm.hip: 128x96 tiles for the part-filling fp32 residual forwards
+    {"gemm_ws", &g_gemm_ws, 0, 4},                 // gemm_ws.hip: the weight-stationary kernel for the K <= 384 wide-N products (2-4: one product)
     {"pk_flags", &g_pk_flags, ANY_LO, ANY_HI},     // gemm_pk.hip: the persistent kernels' epilogue / what-if bits
     {"linear_rows_nb", &g_linear_rows_nb, 0, 2},   // rows_f32.hip: 0 k_linear_f32q (16-row waves), 1 / 2 k_linear_f32t
     {"skip_splitk_reduce", &g_skip_splitk_reduce, ANY_LO, ANY_HI},   // defer.hip: WRONG results, timing only
@@ -324,11 +325,12 @@ const Knob KNOBS[] = {
 };
 
 // product build: automatic (0), the register-staged fallback (2), the persistent 128x128 (9) and 256x256 (24)
-// tiles, k_gemm_f32 for every fp32 product (98: not the small-M or persistent kernels; 97: k_gemm_f32s, not the
+// tiles, the weight-stationary kernel (31: gemm_ws.hip, whatever it takes; the rest as 2),
+// k_gemm_f32 for every fp32 product (98: not the small-M or persistent kernels; 97: k_gemm_f32s, not the
 // K-resident one; 96: the persistent k_gemm_f32p at any M), the generic kernels (99); the measured-slower A/B
 // tiles (among them 26, the 256x256 tile on the staggered 8-phase schedule) only in the A/B build
 bool gemm_variant_in_product(int v) {
-    return v == 0 || v == 2 || v == 9 || v == 24 || v == 96 || v == 97 || v == 98 || v == 99;
+    return v == 0 || v == 2 || v == 9 || v == 24 || v == 31 || v == 96 || v == 97 || v == 98 || v == 99;
 }
 }  // namespace
 
