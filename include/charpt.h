@@ -123,6 +123,10 @@ int cg_set_tuning(const char* key, int value);
 /* launches cg_gemm has run through the weight-stationary kernel (gemm_ws.hip) in this process: for
    tests and A/B tools that must know which kernel served a call                                  */
 int64_t cg_gemm_ws_launches(void);
+/* resident blocks per CU (the runtime's occupancy query) of the weight-stationary instantiation that a
+   product with this B layout, epilogue kind and K / 64 runs (the kernel is built for two 4-wave blocks
+   per CU); -1 if there is none                                                                       */
+int cg_gemm_ws_blocks_per_cu(int b_trans, int kind, int nkt);
 int cg_device_info(int* n_cu, int* arch_major, int* arch_minor);
 /* measurement (bench.py's in-step roofline): a timing event recorded on `stream` -- inside a
    hipGraph capture as an EXTERNAL event-record node (hipEventRecordExternal), so that each replay

@@ -63,6 +63,7 @@ _SIGS = {
     "cg_gemm_colpart_supported": (c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64]),
     "cg_gemm_relu_bits_supported": (c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64]),
     "cg_gemm_ws_launches": (c_i64, []),
+    "cg_gemm_ws_blocks_per_cu": (c_int, [c_int, c_int, c_int]),
     "cg_gemm_rowdot_supported": (c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64]),
     "cg_linear_rows_f32_supported": (c_int, [c_i64, c_i64, c_i64]),
     "cg_decode_qkv_f32": (c_int, [c_i64, c_i64, c_i64, P, c_i64, P, P, c_flt, P, c_i64, P, c_i64, P, c_i64, P, P, P]),

@@ -177,6 +177,8 @@ extern "C" int cg_gemm_relu_bits_supported(int a_trans, int b_trans, int64_t M, 
 
 extern "C" int64_t cg_gemm_ws_launches(void) { return (int64_t)ws_gemm_launches(); }
 
+extern "C" int cg_gemm_ws_blocks_per_cu(int b_trans, int kind, int nkt) { return ws_gemm_blocks_per_cu(b_trans, kind, nkt); }
+
 extern "C" int cg_gemm_rowdot_supported(int a_trans, int b_trans, int64_t M, int64_t N, int64_t K, int64_t lda,
                                         int64_t ldb, int64_t ldc) {
     return gemm_rowdot_supported(a_trans, b_trans, M, N, K, lda, ldb, ldc) ? 1 : 0;

@@ -332,6 +332,8 @@ bool ws_gemm_auto(int64_t M, int64_t N, int kind);
 bool ws_gemm_launch(int at, int bt, int64_t M, int64_t N, int64_t K, const bf16_t* A, int64_t lda, const bf16_t* B,
                     int64_t ldb, void* C, int c_dtype, int64_t ldc, const EpiArgs& e, int split_k, hipStream_t st);
 long long ws_gemm_launches();
+// what the occupancy query says of an instantiation: two resident blocks per CU is the kernel's design
+int ws_gemm_blocks_per_cu(int bt, int kind, int nkt);
 
 // One problem of a grouped split-K weight-gradient launch (cg_gemm_wgrad_group; gemm_pk_group.hip):
 // slabs[s][M][N] = sum over split s's K-tiles of A[k][m] B[k][n].  The caller fills everything but

@@ -9,6 +9,7 @@ variants: single          one graph: fwd + bwd (+ early AdamW) + AdamW (the 1-GP
           <v>:<knob>=<int>  variant v captured with cg_set_tuning(knob, int) (reset to 0 after its
                            capture; the kernel choice / arguments it sets are baked into the graphs);
                            <v>:Fn.<NAME>=<int>  the same with a functional.py module switch (e.g. GEMM_LN)
+                           <v>:<knob>=<int>+<knob>=<int>  several cg_set_tuning knobs for one variant
 usage: python tools/step_ab.py [c2|c4] single,seg1,seg2 [rounds] [steps]"""
 import json
 import os
@@ -24,10 +25,15 @@ from replicatinggpt_amd.data import BatchSampler, TokenStream  # noqa: E402
 from replicatinggpt_amd.engine import GradReducer, TrainStep  # noqa: E402
 
 
+KNOB_DEFAULTS = {b"attn_bwd_lpt": 1, b"gemm_ws": 1}   # cg_set_tuning knobs whose default is not 0
+
+
 def make(variant, cfgname, dev):
-    knob = None
+    knob, more = None, []
     if ":" in variant:
         variant, kv = variant.split(":", 1)
+        kv, *rest = kv.split("+")
+        more = [(x.split("=")[0].encode(), int(x.split("=")[1])) for x in rest]
         k, v = kv.split("=")
         knob = (k.encode(), int(v))
         if k.startswith("Fn."):
@@ -35,8 +41,11 @@ def make(variant, cfgname, dev):
             knob = (k, getattr(Fn, k[3:]))
             setattr(Fn, k[3:], type(knob[1])(int(v)))
         else:
-            from replicatinggpt_amd import _lib as L
-            L.check(L.load().cg_set_tuning(knob[0], knob[1]), "tuning")
+            more.insert(0, knob)
+            knob = None
+        from replicatinggpt_amd import _lib as L
+        for key, val in more:
+            L.check(L.load().cg_set_tuning(key, val), "tuning")
     cfg = PRESETS[cfgname].with_(dtype="bf16")
     torch.manual_seed(cfg.seed)
     model = BigramLanguageModel(cfg).to(dev)
@@ -53,12 +62,12 @@ def make(variant, cfgname, dev):
     else:
         raise ValueError(variant)
     step.capture()
-    if knob is not None and isinstance(knob[0], str):
+    if knob is not None:
         from replicatinggpt_amd import functional as Fn
         setattr(Fn, knob[0][3:], knob[1])   # restore the module switch
-    elif knob is not None:
+    for key, _ in more:   # back to the knob's default
         from replicatinggpt_amd import _lib as L
-        L.check(L.load().cg_set_tuning(knob[0], 1 if knob[0] == b"attn_bwd_lpt" else 0), "tuning")
+        L.check(L.load().cg_set_tuning(key, KNOB_DEFAULTS.get(key, 0)), "tuning")
     return step
 
 
