@@ -175,6 +175,22 @@ int64_t cg_embed_bwd_workspace(int64_t B, int64_t T, int64_t C, int64_t V);
 int cg_embed_bwd(const int64_t* idx, const float* dx, float* dwte, float* dwpe, int64_t B, int64_t T,
                  int64_t C, int64_t V, int accumulate, void* workspace, void* stream);
 
+/* ---- packed rows: several (prompt, completion) pairs per row --------------------------------
+   A row of T tokens is a concatenation of segments, described by seg_start int32 [B, T]:
+   seg_start[b,t] = the index of the first token of the segment that holds position t -- non-decreasing
+   along a row, constant on a segment, <= t.  cg_seg_bounds derives seg_end[b,t] (int32 [B, T], the
+   exclusive end of t's segment) on the device; one launch per forward serves every layer.
+   Positions restart at each segment: x[b,t,:] = wte[idx[b,t],:] + wpe[t - seg_start[b,t],:], and
+   dwpe[p,:] (=|+=) the sum of dx[b,t,:] over all (b, t) with t - seg_start[b,t] = p, in (b, segment)
+   order -- deterministic, any T; dwte as cg_embed_bwd (same workspace).  Out-of-contract bounds are
+   clamped (position into [0, T), seg_end into (t, T]): wrong numbers, never an access outside the
+   operands.  Attention with the same mask: cg_attn_fwd_seg / cg_attn_bwd_seg below.              */
+int cg_seg_bounds(const int32_t* seg_start, int32_t* seg_end, int64_t B, int64_t T, void* stream);
+int cg_embed_fwd_seg(const int64_t* idx, const int32_t* seg_start, const float* wte, const float* wpe, float* x,
+                     int64_t B, int64_t T, int64_t C, int64_t V, void* stream);
+int cg_embed_bwd_seg(const int64_t* idx, const int32_t* seg_end, const float* dx, float* dwte, float* dwpe,
+                     int64_t B, int64_t T, int64_t C, int64_t V, int accumulate, void* workspace, void* stream);
+
 /* ---- LayerNorm (nn.LayerNorm, GPT1.py:159-160,173) -------------------------------------- */
 /* y = (x-mu)*rstd*w + b, biased variance, eps; y dtype y_dtype; saves mean/rstd [rows]     */
 int cg_layernorm_fwd(const float* x, const float* w, const float* b, void* y, int y_dtype, float* mean,
@@ -372,6 +388,29 @@ int cg_attn_bwd_delta(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, con
                       const float* lse, const float* delta, void* dq, void* dk, void* dv, int64_t ld_dqkv,
                       float scale, double dropout_p, uint64_t seed, const uint64_t* rng_call, int site,
                       const uint64_t* mask, void* workspace, void* stream);
+/* The same for packed rows (seg_start / seg_end int32 [B, T] dense, 4-byte aligned: cg_seg_bounds):
+   query i sees key j iff seg_start[b,i] <= j <= i, so a segment's outputs and gradients are those of
+   its tokens alone in a row of their own; every query sees at least itself.  The dropout keep bits
+   stay indexed by (b, h, query, key) of the whole row (same `mask` buffer and cg_attn_dropmask).
+   All-zero seg_start gives the bits of the entry points above.  bf16, head_size 64, T in {64, 128,
+   192, 256} runs the sequence-resident MFMA kernels (the backward always as one launch; `delta`, if
+   given, is read there), longer rows the ring kernels, fp32 with head_size <= 32 and no dropout the
+   fp32 MFMA forward, every other shape the generic kernels -- the family of the unsegmented call.
+   The attn_variant tuning knob does not apply.  cg_attn_bwd_seg's `delta` may be NULL.  stride_* are
+   the row strides in elements, ld_* of the entry points above.                                   */
+int cg_attn_fwd_seg(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const void* q, const void* k,
+                    const void* v, int64_t stride_qkv, void* o, int64_t stride_o, float* lse, float scale, double dropout_p,
+                    uint64_t seed, const uint64_t* rng_call, int site, uint64_t* mask, const int32_t* seg_start,
+                    const int32_t* seg_end, void* stream);
+int cg_attn_fwd_seg_premasked(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const void* q, const void* k,
+                              const void* v, int64_t stride_qkv, void* o, int64_t stride_o, float* lse, float scale,
+                              double dropout_p, uint64_t seed, const uint64_t* rng_call, int site, uint64_t* mask,
+                              const int32_t* seg_start, const int32_t* seg_end, void* stream);
+int cg_attn_bwd_seg(int dtype, int64_t B, int64_t T, int64_t H, int64_t D, const void* q, const void* k,
+                    const void* v, int64_t stride_qkv, const void* o, int64_t stride_o, const void* dout, int64_t stride_do,
+                    const float* lse, const float* delta, void* dq, void* dk, void* dv, int64_t stride_dqkv, float scale,
+                    double dropout_p, uint64_t seed, const uint64_t* rng_call, int site, const uint64_t* mask,
+                    const int32_t* seg_start, const int32_t* seg_end, void* workspace, void* stream);
 
 /* ---- cross entropy over the char vocabulary (F.cross_entropy, GPT1.py:189-192) ----------
    logits fp32 [rows, V] (row stride ld); loss_rows[r] = lse_r - logit[r, tgt_r]; lse saved.

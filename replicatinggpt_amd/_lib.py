@@ -50,6 +50,9 @@ _SIGS = {
     "cg_embed_fwd": (c_int, [P, P, P, P, c_i64, c_i64, c_i64, c_i64, P]),
     "cg_embed_bwd_workspace": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     "cg_embed_bwd": (c_int, [P, P, P, P, c_i64, c_i64, c_i64, c_i64, c_int, P, P]),
+    "cg_seg_bounds": (c_int, [P, P, c_i64, c_i64, P]),
+    "cg_embed_fwd_seg": (c_int, [P, P, P, P, P, c_i64, c_i64, c_i64, c_i64, P]),
+    "cg_embed_bwd_seg": (c_int, [P, P, P, P, P, c_i64, c_i64, c_i64, c_i64, c_int, P, P]),
     "cg_layernorm_fwd": (c_int, [P, P, P, P, c_int, P, P, c_i64, c_i64, c_flt, P]),
     "cg_layernorm_bwd_workspace": (c_i64, [c_i64, c_i64]),
     "cg_layernorm_bwd": (c_int, [P, c_int, P, P, P, P, P, P, P, P, P, c_int, P, c_i64, c_i64, P]),
@@ -97,6 +100,12 @@ _SIGS = {
                             c_flt, c_dbl, c_u64, P, c_int, P, P, P]),
     "cg_attn_bwd_delta": (c_int, [c_int, c_i64, c_i64, c_i64, c_i64, P, P, P, c_i64, P, c_i64, P, c_i64, P, P, P, P,
                                   P, c_i64, c_flt, c_dbl, c_u64, P, c_int, P, P, P]),
+    "cg_attn_fwd_seg": (c_int, [c_int, c_i64, c_i64, c_i64, c_i64, P, P, P, c_i64, P, c_i64, P, c_flt, c_dbl, c_u64,
+                                P, c_int, P, P, P, P]),
+    "cg_attn_fwd_seg_premasked": (c_int, [c_int, c_i64, c_i64, c_i64, c_i64, P, P, P, c_i64, P, c_i64, P, c_flt,
+                                          c_dbl, c_u64, P, c_int, P, P, P, P]),
+    "cg_attn_bwd_seg": (c_int, [c_int, c_i64, c_i64, c_i64, c_i64, P, P, P, c_i64, P, c_i64, P, c_i64, P, P, P, P, P,
+                                c_i64, c_flt, c_dbl, c_u64, P, c_int, P, P, P, P, P]),
     "cg_ce_fwd": (c_int, [P, c_i64, c_i64, c_i64, P, P, P, P]),
     "cg_ce_bwd": (c_int, [P, c_i64, c_i64, c_i64, P, P, P, c_flt, P, c_i64, P, P]),
     "cg_head_workspace": (c_i64, [c_i64, c_i64]),

@@ -75,14 +75,21 @@ void launch_dropmask(int64_t B, int64_t H, int64_t T, uint64_t* mask, const Drop
 void launch_fwd_f32(int64_t B, int64_t T, int H, int D, const float* q, const float* k, const float* v, int64_t ld,
                     float* o, int64_t ldo, float* lse, float scale, hipStream_t st);
 
+// the same on packed rows (seg_start int32 [B][T]): the 64-query-block kernel, launch_fwd_f32's bits for
+// an all-zero seg_start
+void launch_fwd_f32_seg(int64_t B, int64_t T, int H, int D, const float* q, const float* k, const float* v, int64_t ld,
+                        float* o, int64_t ldo, float* lse, float scale, const int32_t* seg_start, hipStream_t st);
+
 // fp32-math VALU kernels, any D <= 128 and any T, dtype CG_BF16 or CG_F32 (attention_generic.hip); the
-// backward computes delta = rowsum(dO * O) into `delta` first
+// backward computes delta = rowsum(dO * O) into `delta` first.  seg_start / seg_end (int32 [B][T], both
+// or neither): the packed-row mask, query i sees key j iff seg_start[b, i] <= j <= i
 void launch_fwd_generic(int dtype, int64_t B, int64_t T_, int H, int D, const void* q, const void* k, const void* v,
-                        int64_t ld, void* o, int64_t ldo, float* lse, float scale, const DropArgs& d, hipStream_t st);
+                        int64_t ld, void* o, int64_t ldo, float* lse, float scale, const DropArgs& d, hipStream_t st,
+                        const int32_t* seg_start = nullptr);
 void launch_bwd_generic(int dtype, int64_t B, int64_t T_, int H, int D, const void* q, const void* k, const void* v,
                         int64_t ld, const void* o, int64_t ldo, const void* dout, int64_t ldd, const float* lse,
                         float* delta, void* dq, void* dk, void* dv, int64_t lddqkv, float scale, const DropArgs& d,
-                        hipStream_t st);
+                        hipStream_t st, const int32_t* seg_start = nullptr, const int32_t* seg_end = nullptr);
 
 // bf16 MFMA kernels, head_size 64, T % 64 == 0 (attention_d64.hip)
 void launch_fwd_d64(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld,
@@ -94,6 +101,17 @@ void launch_bwd_d64(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* 
                     const bf16_t* o, int64_t ldo, const bf16_t* dout, int64_t ldd, const float* lse, float* delta,
                     bool delta_ready, bf16_t* dq, int64_t lddq, bf16_t* dk, bf16_t* dv, int64_t lddkv, float scale, const DropArgs& d,
                     hipStream_t st);
+// packed rows (seg_start / seg_end int32 [B][T]): the sequence-resident kernels at T <= 256
+// (seg_resident: the backward is the merged launch, delta_ready as launch_bwd_d64), the ring kernels
+// beyond (delta is computed into `delta`; delta_ready must be false)
+bool seg_resident(int64_t T);
+void launch_fwd_d64_seg(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld,
+                        bf16_t* o, int64_t ldo, float* lse, float scale, const DropArgs& d, const int32_t* seg_start,
+                        const int32_t* seg_end, hipStream_t st);
+void launch_bwd_d64_seg(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld,
+                        const bf16_t* o, int64_t ldo, const bf16_t* dout, int64_t ldd, const float* lse, float* delta,
+                        bool delta_ready, bf16_t* dq, int64_t lddq, bf16_t* dk, bf16_t* dv, int64_t lddkv, float scale,
+                        const DropArgs& d, const int32_t* seg_start, const int32_t* seg_end, hipStream_t st);
 }  // namespace attn
 // cg_set_tuning knobs (attention_d64.hip)
 extern int g_attn_variant;

@@ -29,6 +29,53 @@ static void with_nt_drop(int64_t T, const DropArgs& d, F&& f) {
     with_nt(T, [&](auto nt) { with_drop(d, [&](auto drop) { f(nt, drop); }); });
 }
 
+// packed rows: the sequence-resident kernels at T <= 256 and the ring kernels beyond, whatever
+// attn_variant says; seg_resident: the backward is the merged launch, which can read a given delta
+bool seg_resident(int64_t T) { return T <= 256; }
+
+void launch_fwd_d64_seg(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld,
+                        bf16_t* o, int64_t ldo, float* lse, float scale, const DropArgs& d, const int32_t* seg_start,
+                        const int32_t* seg_end, hipStream_t st) {
+    if (!seg_resident(T)) {
+        const dim3 grid((unsigned)((ceil_div(T, 256) + 1) / 2), (unsigned)(B * H));
+        with_drop(d, [&](auto drop) {
+            k_attn_fwd_d64d_seg<decltype(drop)::value><<<grid, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, lse, scale * LOG2E,
+                                                                              d.mask, d.dscale, seg_start, seg_end);
+        });
+        return;
+    }
+    with_nt_drop(T, d, [&](auto nt, auto drop) {
+        k_attn_fwd_d64r_seg<decltype(drop)::value, decltype(nt)::value><<<dim3(1, (unsigned)(B * H)), 256, 0, st>>>(
+            H, q, k, v, ld, o, ldo, lse, scale * LOG2E, d.mask, d.dscale, seg_start, seg_end);
+    });
+}
+
+void launch_bwd_d64_seg(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld,
+                        const bf16_t* o, int64_t ldo, const bf16_t* dout, int64_t ldd, const float* lse, float* delta,
+                        bool delta_ready, bf16_t* dq, int64_t lddq, bf16_t* dk, bf16_t* dv, int64_t lddkv, float scale,
+                        const DropArgs& d, const int32_t* seg_start, const int32_t* seg_end, hipStream_t st) {
+    if (!seg_resident(T)) {   // dQ (writes delta), then dK/dV, as launch_dq_d64 / launch_dkdv_d64
+        const dim3 gq((unsigned)((ceil_div(T, 256) + 1) / 2), (unsigned)(B * H));
+        const dim3 gk((unsigned)((ceil_div(T, 128) + 1) / 2), (unsigned)(B * H));
+        with_drop(d, [&](auto drop) {
+            k_attn_dq_d64_seg<decltype(drop)::value, 4><<<gq, 256, 0, st>>>(T, H, q, k, v, ld, o, ldo, dout, ldd, lse, delta,
+                                                                             dq, lddq, scale, d.mask, d.dscale, seg_start);
+            k_attn_dkdv_d64_seg<decltype(drop)::value, 4><<<gk, 256, 0, st>>>(T, H, q, k, v, ld, dout, ldd, lse, delta, dk,
+                                                                               dv, lddkv, scale, d.mask_bwd, d.dscale,
+                                                                               seg_end);
+        });
+        return;
+    }
+    const dim3 grid(1, (unsigned)(2 * B * H));
+    with_nt_drop(T, d, [&](auto nt, auto drop) {
+        with_flag(delta_ready, [&](auto din) {
+            k_attn_bwd_d64r_seg<decltype(drop)::value, decltype(nt)::value, decltype(din)::value>
+                <<<grid, 256, 0, st>>>(H, q, k, v, ld, o, ldo, dout, ldd, lse, delta, dq, lddq, dk, dv, lddkv, scale,
+                                       d.mask, d.mask_bwd, d.dscale, g_attn_bwd_lpt, seg_start, seg_end);
+        });
+    });
+}
+
 void launch_fwd_d64(int64_t B, int64_t T, int H, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ld,
                     bf16_t* o, int64_t ldo, float* lse, float scale, const DropArgs& d, hipStream_t st) {
     if (resident(T)) {

@@ -160,6 +160,148 @@ __global__ __launch_bounds__(256, 2) void k_attn_fwd_d64r(int H, const bf16_t* _
     ATTN_STAMP(3, attn_where(2));
 }
 
+// The same on packed rows (k_attn_fwd_d64r_seg; a copy of the kernel above rather than a template flag
+// on it: sharing the body moved the unsegmented kernels' register allocation -- so SEG is always true
+// here, and marks the lines the copy adds).  Each lane also loads its queries' seg_start / seg_end
+// (int32 [B][T]) with the other register operands; key tiles wholly before every lane's segment are
+// skipped, the others masked per lane (fwd_group_tile).
+template <bool DROP, int NT, bool SEG>
+__device__ __forceinline__ void fwd_res(int H, const bf16_t* __restrict__ q,
+                                        const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int64_t ld,
+                                        bf16_t* __restrict__ o, int64_t ldo, float* __restrict__ lse,
+                                        float scale_log2, const uint32_t* __restrict__ mask, float dscale,
+                                        const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_end) {
+    constexpr int T = 64 * NT;
+    __shared__ __attribute__((aligned(16))) char smem[NT * 2 * TILE];   // K, V images of tile t at 2 t TILE
+    ATTN_STAMP(0, attn_now());
+    int x, bh;
+    block_coords<false>(x, bh);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = bh / H, hh = bh % H;
+    const int64_t boff = (int64_t)b * T, ntile = mask_tiles(T);
+    const int qg[2] = {32 * (7 - wave), 32 * wave};   // A = 7 - w (longer causal prefix), B = w
+    const bool act[2] = {qg[0] < T, qg[1] < T};
+    sv8 qv[2][4];
+    uint32_t mw[2][NT], ssw[2] = {0u, 0u}, sew[2] = {0u, 0u};
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const int qa = (act[g] ? qg[g] : 0) + (lane & 31);   // inactive groups load a valid row, unused
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) gload16(qv[g][ks], q + (boff + qa) * ld + hh * 64 + 16 * ks + 8 * (lane >> 5));
+        if constexpr (SEG) {
+            gload4(ssw[g], seg_start + boff + qa);
+            gload4(sew[g], seg_end + boff + qa);
+        }
+        if constexpr (DROP) {
+            const int qb = act[g] ? qg[g] >> 5 : 0;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {   // tiles past the group's diagonal re-read tile 0 (unused)
+                const int tt = 64 * t <= 32 * qb + 31 ? t : 0;
+                gload4(mw[g][t], mask + ((int64_t)bh * ntile + mask_fwd_tile(qb, tt)) * 64 + lane);
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        dma_tile(k + boff * ld + hh * 64, ld, 64 * t, lds_base(smem) + 2u * t * TILE, wave, lane);
+        dma_tile(v + boff * ld + hh * 64, ld, 64 * t, lds_base(smem) + (2u * t + 1) * TILE, wave, lane);
+    }
+    // the register loads and tile 0 have landed (4 DMA instructions per tile per wave stay younger)
+    if constexpr (!DROP) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) mw[g][t] = 0u;
+    }
+    // then every destination is named "+v" by an (ordered, volatile) empty statement after the wait,
+    // so nothing reads it earlier
+    asm volatile("s_waitcnt vmcnt(%c0)\n\ts_barrier" ::"i"(4 * (NT - 1)) : "memory");
+    ATTN_STAMP(1, attn_now());
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qv[g][ks]));
+#pragma unroll
+        for (int t = 0; t < NT; ++t) asm volatile("" : "+v"(mw[g][t]));
+        if constexpr (SEG) asm volatile("" : "+v"(ssw[g]), "+v"(sew[g]));
+    }
+    int ss[2] = {0, 0};
+    uint32_t peers[2] = {0u, 0u};
+    if constexpr (SEG) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            if (!act[g]) continue;
+            const int qa = qg[g] + (lane & 31);
+            ss[g] = seg_lo(ssw[g], qa);
+            peers[g] = seg_peers(ss[g], seg_hi(sew[g], qa), qg[g]);
+        }
+    }
+    const sv8 (&qf)[2][4] = qv;
+    fv16 oacc[2][2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) oacc[g][0] = oacc[g][1] = fv16{};
+    float m_run[2] = {-FLT_MAX, -FLT_MAX};
+    fv4 l_run[2] = {fv4{}, fv4{}};
+    const sv8 ones = rowsum_ones(lane);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if (t) {   // tile t's DMAs (every wave's) have landed
+            if constexpr (NT >= 2) {
+                if (t == 1) asm volatile("s_waitcnt vmcnt(%c0)\n\ts_barrier" ::"i"(4 * (NT > 1 ? NT - 2 : 0)) : "memory");
+            }
+            if constexpr (NT >= 3) {
+                if (t == 2) asm volatile("s_waitcnt vmcnt(%c0)\n\ts_barrier" ::"i"(4 * (NT > 2 ? NT - 3 : 0)) : "memory");
+            }
+            if constexpr (NT >= 4) {
+                if (t == 3) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+            }
+        }
+        const char* Ki = smem + 2 * t * TILE;
+        const char* Vi = Ki + TILE;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            if (!act[g] || 64 * t > qg[g] + 31) continue;
+            const int rel = __builtin_amdgcn_readfirstlane(qg[g] - 64 * t);
+            const int srel = SEG ? ss[g] - 64 * t : 0;
+            if constexpr (SEG) {
+                if (__all(srel >= 64)) continue;   // the tile precedes every lane's segment
+            }
+            if (rel >= 64)
+                fwd_group_tile<DROP, 2, -1, true, SEG>(Ki, Vi, nullptr, 0, lane, scale_log2, m_run[g], l_run[g],
+                                                       oacc[g], mw[g][t], ones, qf[g], srel, peers[g]);
+            else if (rel == 32)
+                fwd_group_tile<DROP, 2, 1, true, SEG>(Ki, Vi, nullptr, 0, lane, scale_log2, m_run[g], l_run[g],
+                                                      oacc[g], mw[g][t], ones, qf[g], srel, peers[g]);
+            else
+                fwd_group_tile<DROP, 1, 0, true, SEG>(Ki, Vi, nullptr, 0, lane, scale_log2, m_run[g], l_run[g],
+                                                      oacc[g], mw[g][t], ones, qf[g], srel, peers[g]);
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        if (!act[g]) continue;
+        const float lt = l_run[g][0];   // every accumulator register holds query lane & 31's sum
+        const int64_t qa = qg[g] + (lane & 31);
+        store_rows_wide(o + (boff + qa) * ldo + hh * 64, oacc[g], dscale / lt, lane);
+        if (lane < 32) lse[(int64_t)bh * T + qa] = (m_run[g] + __log2f(lt)) * LN2;
+    }
+    ATTN_STAMP(2, attn_now());
+    ATTN_STAMP(3, attn_where(2));
+}
+
+template <bool DROP, int NT>
+__global__ __launch_bounds__(256, 2) void k_attn_fwd_d64r_seg(int H, const bf16_t* __restrict__ q,
+                                                              const bf16_t* __restrict__ k,
+                                                              const bf16_t* __restrict__ v, int64_t ld,
+                                                              bf16_t* __restrict__ o, int64_t ldo,
+                                                              float* __restrict__ lse, float scale_log2,
+                                                              const uint32_t* __restrict__ mask, float dscale,
+                                                              const int32_t* __restrict__ seg_start,
+                                                              const int32_t* __restrict__ seg_end) {
+    fwd_res<DROP, NT, true>(H, q, k, v, ld, o, ldo, lse, scale_log2, mask, dscale, seg_start, seg_end);
+}
+
 // tile t > 0 of a resident kernel: this wave's DMAs of tiles 0..t have landed (4 DMA instructions per
 // tile per wave, issued in tile order after the first register loads; X hidden loads issued after the
 // DMAs stay in flight too), then every wave's (barrier)
@@ -180,13 +322,14 @@ __device__ __forceinline__ void res_tile_wait(int t) {
 // by hidden register loads first, then the K/V tiles by LDS-DMA in tile order; tile t waits only
 // for tiles 0..t (as k_attn_fwd_d64r).  Per-group setup (delta in dq_group_setup's summation order)
 // and per-tile arithmetic as the ring kernel.
-template <bool DROP, int NT, bool DIN = false>
+template <bool DROP, int NT, bool DIN = false, bool SEG = false>
 __device__ __forceinline__ void dq_res(int bh, char* smem, int H, const bf16_t* __restrict__ q,
                                        const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int64_t ld,
                                        const bf16_t* __restrict__ o, int64_t ldo, const bf16_t* __restrict__ dout,
                                        int64_t ldd, const float* __restrict__ lse, float* __restrict__ delta,
                                        bf16_t* __restrict__ dq, int64_t lddq, float scale,
-                                       const uint32_t* __restrict__ mask, float dscale) {
+                                       const uint32_t* __restrict__ mask, float dscale,
+                                       const int32_t* __restrict__ seg_start = nullptr) {
     constexpr int T = 64 * NT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -196,7 +339,7 @@ __device__ __forceinline__ void dq_res(int bh, char* smem, int H, const bf16_t* 
     const int qg[2] = {32 * (7 - wave), 32 * wave};
     const bool act[2] = {qg[0] < T, qg[1] < T};
     sv8 qf[2][4], df[2][4], of[2][4];
-    uint32_t lsew[2], delw[2] = {0u, 0u}, mw[2][NT];
+    uint32_t lsew[2], delw[2] = {0u, 0u}, mw[2][NT], ssw[2] = {0u, 0u};
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
         const int64_t qa = (act[g] ? qg[g] : 0) + (lane & 31);   // inactive groups: a valid row, unused
@@ -209,6 +352,7 @@ __device__ __forceinline__ void dq_res(int bh, char* smem, int H, const bf16_t* 
         }
         gload4(lsew[g], lse + (int64_t)bh * T + qa);
         if constexpr (DIN) gload4(delw[g], delta + (int64_t)bh * T + qa);
+        if constexpr (SEG) gload4(ssw[g], seg_start + boff + qa);
         if constexpr (DROP) {
             const int qb = act[g] ? qg[g] >> 5 : 0;
 #pragma unroll
@@ -240,6 +384,7 @@ __device__ __forceinline__ void dq_res(int bh, char* smem, int H, const bf16_t* 
             if constexpr (!DIN) asm volatile("" : "+v"(of[g][ks]));
         }
         asm volatile("" : "+v"(lsew[g]), "+v"(delw[g]));
+        if constexpr (SEG) asm volatile("" : "+v"(ssw[g]));
 #pragma unroll
         for (int t = 0; t < NT; ++t) asm volatile("" : "+v"(mw[g][t]));
     }
@@ -271,8 +416,8 @@ __device__ __forceinline__ void dq_res(int bh, char* smem, int H, const bf16_t* 
 #pragma unroll
         for (int g = 0; g < 2; ++g)
             if (act[g] && 64 * t <= qg[g] + 31)
-                dq_group_tile<DROP>(Ki, Ki + TILE, 64 * t, qg[g], qf[g], df[g], lse2[g], dl[g], mw[g][t], c2, dqa[g],
-                                    lane);
+                dq_group_tile<DROP, SEG>(Ki, Ki + TILE, 64 * t, qg[g], qf[g], df[g], lse2[g], dl[g], mw[g][t], c2,
+                                         dqa[g], lane, SEG ? seg_lo(ssw[g], qg[g] + (lane & 31)) : 0);
     }
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
@@ -303,13 +448,14 @@ __global__ __launch_bounds__(256, 2) void k_attn_dq_d64r(int H, const bf16_t* __
 // Register operands (row statistics, the first key group's K / V fragments, keep words) by hidden
 // loads first, then the Q / dO tiles by LDS-DMA; the first key group's tile t waits only for tiles
 // 0..t.  OD: delta from O and dO (o != NULL), else read from `delta`.
-template <bool DROP, int NT, bool OD>
+template <bool DROP, int NT, bool OD, bool SEG = false>
 __device__ __forceinline__ void dkdv_res(int bh, char* smem, int H, const bf16_t* __restrict__ q,
                                          const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int64_t ld,
                                          const bf16_t* __restrict__ dout, int64_t ldd, const float* __restrict__ lse,
                                          const float* __restrict__ delta, const bf16_t* __restrict__ o, int64_t ldo,
                                          bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int64_t lddkv, float scale,
-                                         const uint32_t* __restrict__ mask, float dscale) {
+                                         const uint32_t* __restrict__ mask, float dscale,
+                                         const int32_t* __restrict__ seg_end = nullptr) {
     constexpr int T = 64 * NT;
     float* st_lse = (float*)(smem + NT * 2 * TILE);
     float* st_del = st_lse + T;
@@ -353,6 +499,11 @@ __device__ __forceinline__ void dkdv_res(int bh, char* smem, int H, const bf16_t
             }
         }
     }
+    uint32_t sew[2] = {0u, 0u};   // SEG: the segment end of this lane's key, per key group
+    if constexpr (SEG) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) gload4(sew[p], seg_end + boff + (kqs[p] < T ? kqs[p] : 0) + (lane & 31));
+    }
     sv8 kf[4], vf[4];
     {
         const int key0 = (kqs[0] < T ? kqs[0] : 0) + (lane & 31);
@@ -379,6 +530,7 @@ __device__ __forceinline__ void dkdv_res(int bh, char* smem, int H, const bf16_t
     }
     asm volatile("s_waitcnt vmcnt(%c0)" ::"i"(4 * (NT - 1) + 8) : "memory");
     asm volatile("" : "+v"(lsew), "+v"(delw));
+    if constexpr (SEG) asm volatile("" : "+v"(sew[0]), "+v"(sew[1]));
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -444,8 +596,9 @@ __device__ __forceinline__ void dkdv_res(int bh, char* smem, int H, const bf16_t
         for (int t = 0; t < NT; ++t) {
             if (!p) res_tile_wait<NT, 8>(t);
             if (act && 64 * t + 63 >= kq)
-                dkdv_tile<DROP>(smem + 2 * t * TILE, smem + (2 * t + 1) * TILE, st_lse + 64 * t, st_del + 64 * t,
-                                64 * t, kq, key, kf, vf, mw[p][t], c2, dka, dva, lane);
+                dkdv_tile<DROP, SEG>(smem + 2 * t * TILE, smem + (2 * t + 1) * TILE, st_lse + 64 * t, st_del + 64 * t,
+                                     64 * t, kq, key, kf, vf, mw[p][t], c2, dka, dva, lane,
+                                     SEG ? seg_hi(sew[p], key) : 0);
         }
         if (act) {
             store_rows_wide(dk + (boff + key) * lddkv + hh * 64, dka, scale * dscale, lane);
@@ -475,18 +628,16 @@ __global__ __launch_bounds__(256, 2) void k_attn_dkdv_d64r(int H, const bf16_t* 
 // workgroups fill the 512 slots and the second wave of them starts as slots free up, where the
 // two separate 384-workgroup launches each ran 3/4 full and back to back.  The pair of one (b, h)
 // stays on one XCD (block_coords: consecutive logical ids), sharing its K/V/Q/dO lines in L2.
-template <bool DROP, int NT, bool DIN>
-__global__ __launch_bounds__(256, 2) void k_attn_bwd_d64r(int H, const bf16_t* __restrict__ q,
-                                                          const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
-                                                          int64_t ld, const bf16_t* __restrict__ o, int64_t ldo,
-                                                          const bf16_t* __restrict__ dout, int64_t ldd,
-                                                          const float* __restrict__ lse, float* __restrict__ delta,
-                                                          bf16_t* __restrict__ dq, int64_t lddq, bf16_t* __restrict__ dk,
-                                                          bf16_t* __restrict__ dv, int64_t lddkv, float scale,
-                                                          const uint32_t* __restrict__ mask_fwd,
-                                                          const uint32_t* __restrict__ mask_bwd, float dscale,
-                                                          int lpt) {
-    __shared__ __attribute__((aligned(16))) char smem[NT * 2 * TILE + 2 * 64 * NT * 4];
+template <bool DROP, int NT, bool DIN, bool SEG>
+__device__ __forceinline__ void bwd_res(char* smem, int H, const bf16_t* __restrict__ q,
+                                        const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int64_t ld,
+                                        const bf16_t* __restrict__ o, int64_t ldo, const bf16_t* __restrict__ dout,
+                                        int64_t ldd, const float* __restrict__ lse, float* __restrict__ delta,
+                                        bf16_t* __restrict__ dq, int64_t lddq, bf16_t* __restrict__ dk,
+                                        bf16_t* __restrict__ dv, int64_t lddkv, float scale,
+                                        const uint32_t* __restrict__ mask_fwd, const uint32_t* __restrict__ mask_bwd,
+                                        float dscale, int lpt, const int32_t* __restrict__ seg_start,
+                                        const int32_t* __restrict__ seg_end) {
     ATTN_STAMP(0, attn_now());
     int x, id;
     const int n = (int)gridDim.y, w = (int)blockIdx.y;
@@ -500,13 +651,43 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_d64r(int H, const bf16_t* _
         block_coords<false>(x, id);
     }
     if (id & 1)
-        dkdv_res<DROP, NT, !DIN>(id >> 1, smem, H, q, k, v, ld, dout, ldd, lse, delta, o, ldo, dk, dv, lddkv, scale,
-                                 mask_bwd, dscale);
+        dkdv_res<DROP, NT, !DIN, SEG>(id >> 1, smem, H, q, k, v, ld, dout, ldd, lse, delta, o, ldo, dk, dv, lddkv,
+                                      scale, mask_bwd, dscale, seg_end);
     else
-        dq_res<DROP, NT, DIN>(id >> 1, smem, H, q, k, v, ld, o, ldo, dout, ldd, lse, delta, dq, lddq, scale, mask_fwd,
-                              dscale);
+        dq_res<DROP, NT, DIN, SEG>(id >> 1, smem, H, q, k, v, ld, o, ldo, dout, ldd, lse, delta, dq, lddq, scale,
+                                   mask_fwd, dscale, seg_start);
     ATTN_STAMP(2, attn_now());
     ATTN_STAMP(3, attn_where(id & 1));
+}
+
+template <bool DROP, int NT, bool DIN>
+__global__ __launch_bounds__(256, 2) void k_attn_bwd_d64r(int H, const bf16_t* __restrict__ q,
+                                                          const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                          int64_t ld, const bf16_t* __restrict__ o, int64_t ldo,
+                                                          const bf16_t* __restrict__ dout, int64_t ldd,
+                                                          const float* __restrict__ lse, float* __restrict__ delta,
+                                                          bf16_t* __restrict__ dq, int64_t lddq, bf16_t* __restrict__ dk,
+                                                          bf16_t* __restrict__ dv, int64_t lddkv, float scale,
+                                                          const uint32_t* __restrict__ mask_fwd,
+                                                          const uint32_t* __restrict__ mask_bwd, float dscale,
+                                                          int lpt) {
+    __shared__ __attribute__((aligned(16))) char smem[NT * 2 * TILE + 2 * 64 * NT * 4];
+    bwd_res<DROP, NT, DIN, false>(smem, H, q, k, v, ld, o, ldo, dout, ldd, lse, delta, dq, lddq, dk, dv, lddkv, scale,
+                                  mask_fwd, mask_bwd, dscale, lpt, nullptr, nullptr);
+}
+
+// the same for packed rows: dQ reads seg_start, dK/dV seg_end (int32 [B][T])
+template <bool DROP, int NT, bool DIN>
+__global__ __launch_bounds__(256, 2) void k_attn_bwd_d64r_seg(
+    int H, const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int64_t ld,
+    const bf16_t* __restrict__ o, int64_t ldo, const bf16_t* __restrict__ dout, int64_t ldd,
+    const float* __restrict__ lse, float* __restrict__ delta, bf16_t* __restrict__ dq, int64_t lddq,
+    bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int64_t lddkv, float scale,
+    const uint32_t* __restrict__ mask_fwd, const uint32_t* __restrict__ mask_bwd, float dscale, int lpt,
+    const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_end) {
+    __shared__ __attribute__((aligned(16))) char smem[NT * 2 * TILE + 2 * 64 * NT * 4];
+    bwd_res<DROP, NT, DIN, true>(smem, H, q, k, v, ld, o, ldo, dout, ldd, lse, delta, dq, lddq, dk, dv, lddkv, scale,
+                                 mask_fwd, mask_bwd, dscale, lpt, seg_start, seg_end);
 }
 
 }  // namespace

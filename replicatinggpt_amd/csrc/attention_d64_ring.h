@@ -37,13 +37,15 @@ __device__ __forceinline__ void dq_group_setup(bool act, int64_t qa, const bf16_
 
 // K/V tiles by LDS-DMA (common.h dma16) into a 2-slot ring, the next tile's DMAs issued before the
 // current tile's products (round 2: register staging measured 706 -> 686 us for the C4 backward)
-template <bool DROP, int NS>
+// SEG (packed rows): each lane also holds its queries' segment start (dq_group_tile masks and skips)
+template <bool DROP, int NS, bool SEG = false>
 __device__ __forceinline__ void dq_qblock(int qblk, int bh, char* smem, int64_t T_, int H, const bf16_t* __restrict__ q,
                                           const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int64_t ld,
                                           const bf16_t* __restrict__ o, int64_t ldo, const bf16_t* __restrict__ dout,
                                           int64_t ldd, const float* __restrict__ lse, float* __restrict__ delta,
                                           bf16_t* __restrict__ dq, int64_t lddq, float scale,
-                                          const uint32_t* __restrict__ mask, float dscale) {
+                                          const uint32_t* __restrict__ mask, float dscale,
+                                          const int32_t* __restrict__ seg_start = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int T = (int)T_, b = bh / H, hh = bh % H;
@@ -68,6 +70,12 @@ __device__ __forceinline__ void dq_qblock(int qblk, int bh, char* smem, int64_t 
         dq_group_setup(act[g], qg[g] + (lane & 31), q + boff * ld + hh * 64, ld, o + boff * ldo + hh * 64, ldo,
                        dout + boff * ldd + hh * 64, ldd, lse + (int64_t)bh * T_, delta + (int64_t)bh * T_, dscale, lane,
                        qf[g], df[g], lse2[g], dl[g]);
+    int ss[2] = {0, 0};
+    if constexpr (SEG) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+            if (act[g]) ss[g] = seg_lo((uint32_t)seg_start[boff + qg[g] + (lane & 31)], qg[g] + (lane & 31));
+    }
     fv16 dqa[2][2];
 #pragma unroll
     for (int g = 0; g < 2; ++g) dqa[g][0] = dqa[g][1] = fv16{};
@@ -93,6 +101,7 @@ __device__ __forceinline__ void dq_qblock(int qblk, int bh, char* smem, int64_t 
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) mark_ready(qf[g][ks], df[g][ks]);
     mark_ready(mw[0], mw[1], lse2[0], lse2[1], dl[0], dl[1]);
+    if constexpr (SEG) mark_ready(ss[0], ss[1]);
     for (int kv = 0; kv < nkv; ++kv) {
         const int nxt = kv + 1 < nkv ? kv + 1 : kv;
         // the next tile's keep words by hidden loads, issued before the DMAs so that the counted wait
@@ -114,7 +123,8 @@ __device__ __forceinline__ void dq_qblock(int qblk, int bh, char* smem, int64_t 
 #pragma unroll
         for (int g = 0; g < 2; ++g)
             if (act[g] && k0 <= qg[g] + 31)
-                dq_group_tile<DROP>(Ki, Ki + TILE, k0, qg[g], qf[g], df[g], lse2[g], dl[g], mw[g], c2, dqa[g], lane);
+                dq_group_tile<DROP, SEG>(Ki, Ki + TILE, k0, qg[g], qf[g], df[g], lse2[g], dl[g], mw[g], c2, dqa[g], lane,
+                                         ss[g]);
         ring_wait<AH == 2 ? 4 : 0>(pf);   // tile kv + 1 (and the keep words) have landed for every wave
         asm volatile("" : "+v"(mn[0]), "+v"(mn[1]));
         mw[0] = mn[0];
@@ -150,19 +160,43 @@ __global__ __launch_bounds__(256, 2) void k_attn_dq_d64(int64_t T_, int H, const
     }
 }
 
+template <bool DROP, int NS>
+__global__ __launch_bounds__(256, 2) void k_attn_dq_d64_seg(int64_t T_, int H, const bf16_t* __restrict__ q,
+                                                            const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                            int64_t ld, const bf16_t* __restrict__ o, int64_t ldo,
+                                                            const bf16_t* __restrict__ dout, int64_t ldd,
+                                                            const float* __restrict__ lse, float* __restrict__ delta,
+                                                            bf16_t* __restrict__ dq, int64_t lddq, float scale,
+                                                            const uint32_t* __restrict__ mask, float dscale,
+                                                            const int32_t* __restrict__ seg_start) {
+    __shared__ __attribute__((aligned(16))) char smem[NS * 2 * TILE];
+    int x, bh;
+    block_coords<false>(x, bh);
+    const int nq = (int)((T_ + 255) / 256), first = nq - 1 - x;
+    const int npass = x == first ? 1 : 2;
+#pragma unroll 1
+    for (int pass = 0; pass < npass; ++pass) {
+        if (pass) __syncthreads();
+        dq_qblock<DROP, NS, true>(pass ? x : first, bh, smem, T_, H, q, k, v, ld, o, ldo, dout, ldd, lse, delta, dq, lddq,
+                                  scale, mask, dscale, seg_start);
+    }
+}
+
 // =====================================================================================
 // dK / dV: block = 4 waves x 32 keys; stream 64-query tiles (Q, dO, lse, delta)
 // =====================================================================================
 constexpr int KV_STAGE = 2 * TILE + 512;   // Q image, dO image, lse*log2e [64], delta [64]
 
-template <bool DROP, int NS>
+// SEG (packed rows): each lane also holds the end of its key's segment (dkdv_tile masks and skips)
+template <bool DROP, int NS, bool SEG = false>
 __device__ __forceinline__ void dkdv_kblock(int kblk, int bh, char* smem, int64_t T_, int H,
                                             const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                             const bf16_t* __restrict__ v, int64_t ld, const bf16_t* __restrict__ dout,
                                             int64_t ldd, const float* __restrict__ lse,
                                             const float* __restrict__ delta, bf16_t* __restrict__ dk,
                                             bf16_t* __restrict__ dv, int64_t lddkv, float scale,
-                                            const uint32_t* __restrict__ mask, float dscale) {
+                                            const uint32_t* __restrict__ mask, float dscale,
+                                            const int32_t* __restrict__ seg_end = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int T = (int)T_, b = bh / H, hh = bh % H;
@@ -176,6 +210,10 @@ __device__ __forceinline__ void dkdv_kblock(int kblk, int bh, char* smem, int64_
     for (int ks = 0; ks < 4; ++ks) {
         kf[ks] = act ? ld_frag(k + boff * ld + hh * 64, ld, key, ks, lane) : sv8{};
         vf[ks] = act ? ld_frag(v + boff * ld + hh * 64, ld, key, ks, lane) : sv8{};
+    }
+    int se = 0;
+    if constexpr (SEG) {
+        if (act) se = seg_hi((uint32_t)seg_end[boff + key], key);
     }
     fv16 dka[2] = {fv16{}, fv16{}}, dva[2] = {fv16{}, fv16{}};
     const bf16_t* qb_ = q + boff * ld + hh * 64;
@@ -218,6 +256,7 @@ __device__ __forceinline__ void dkdv_kblock(int kblk, int bh, char* smem, int64_
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) mark_ready(kf[ks], vf[ks]);
     mark_ready(mw);
+    if constexpr (SEG) mark_ready(se);
     for (int qt = qt0; qt < nq; ++qt) {
         const int it = qt - qt0;
         const int nxt = qt + 1 < nq ? qt + 1 : qt;
@@ -241,7 +280,8 @@ __device__ __forceinline__ void dkdv_kblock(int kblk, int bh, char* smem, int64_
         const float* st_lse = (const float*)(S0 + 2 * TILE);
         const float* st_del = st_lse + 64;
         const int q0 = qt * 64;
-        if (act && q0 + 63 >= kq) dkdv_tile<DROP>(Qi, Oi, st_lse, st_del, q0, kq, key, kf, vf, mw, c2, dka, dva, lane);
+        if (act && q0 + 63 >= kq)
+            dkdv_tile<DROP, SEG>(Qi, Oi, st_lse, st_del, q0, kq, key, kf, vf, mw, c2, dka, dva, lane, se);
         // tile qt + 1, the statistics and the keep word have landed (tile qt + AH's DMAs may not)
         if (AH == 2 && pf) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -278,6 +318,29 @@ __global__ __launch_bounds__(256, 2) void k_attn_dkdv_d64(int64_t T_, int H, con
         if (pass) __syncthreads();
         dkdv_kblock<DROP, NS>(pass ? second : x, bh, smem, T_, H, q, k, v, ld, dout, ldd, lse, delta, dk, dv, lddkv, scale,
                           mask, dscale);
+    }
+}
+
+template <bool DROP, int NS>
+__global__ __launch_bounds__(256, 2) void k_attn_dkdv_d64_seg(int64_t T_, int H, const bf16_t* __restrict__ q,
+                                                              const bf16_t* __restrict__ k,
+                                                              const bf16_t* __restrict__ v, int64_t ld,
+                                                              const bf16_t* __restrict__ dout, int64_t ldd,
+                                                              const float* __restrict__ lse,
+                                                              const float* __restrict__ delta, bf16_t* __restrict__ dk,
+                                                              bf16_t* __restrict__ dv, int64_t lddkv, float scale,
+                                                              const uint32_t* __restrict__ mask, float dscale,
+                                                              const int32_t* __restrict__ seg_end) {
+    __shared__ __attribute__((aligned(16))) char smem[NS * KV_STAGE];
+    int x, bh;
+    block_coords<false>(x, bh);
+    const int nk = (int)((T_ + 127) / 128), second = nk - 1 - x;
+    const int npass = x == second ? 1 : 2;
+#pragma unroll 1
+    for (int pass = 0; pass < npass; ++pass) {
+        if (pass) __syncthreads();
+        dkdv_kblock<DROP, NS, true>(pass ? second : x, bh, smem, T_, H, q, k, v, ld, dout, ldd, lse, delta, dk, dv, lddkv,
+                                    scale, mask, dscale, seg_end);
     }
 }
 
@@ -329,12 +392,18 @@ __device__ __forceinline__ void qk_tile_reg(fv16 (&s)[2], const char* Ki, const 
     }
 }
 
-template <bool DROP, bool QR>
+// SEG (packed rows, QR only): the lanes' segment bounds come in with the Q fragments; every tile goes
+// through fwd_group_tile (no two-group pipeline: the same per-group arithmetic in the same order, so
+// an all-zero seg_start gives the pipelined kernel's bits), tiles before every lane's segment skipped
+template <bool DROP, bool QR, bool SEG = false>
 __device__ __forceinline__ void fwd_qblock_dma(int qblk, int bh, char* smem, int64_t T_, int H,
                                                const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                const bf16_t* __restrict__ v, int64_t ld, bf16_t* __restrict__ o,
                                                int64_t ldo, float* __restrict__ lse, float scale_log2,
-                                               const uint32_t* __restrict__ mask, float dscale) {
+                                               const uint32_t* __restrict__ mask, float dscale,
+                                               const int32_t* __restrict__ seg_start = nullptr,
+                                               const int32_t* __restrict__ seg_end = nullptr) {
+    static_assert(QR || !SEG, "the segment mask is built for the register-Q form");
     using R = FwdRing<QR>;
     constexpr int AH = R::AHEAD;
     // tile kv + AH is requested at tile kv: 4 DMA instructions per wave stay in flight at its end
@@ -362,7 +431,7 @@ __device__ __forceinline__ void fwd_qblock_dma(int qblk, int bh, char* smem, int
     const uint32_t* mrow[2];
     const uint32_t loff = 4u * lane;
     sv8 qf[2][4];
-    uint32_t mw[2] = {0u, 0u};
+    uint32_t mw[2] = {0u, 0u}, ssw[2] = {0u, 0u}, sew[2] = {0u, 0u};
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
         mrow[g] = mask + ((int64_t)bh * ntile + mask_fwd_tile(act[g] ? qg[g] >> 5 : 0, 0)) * 64;
@@ -370,12 +439,16 @@ __device__ __forceinline__ void fwd_qblock_dma(int qblk, int bh, char* smem, int
             const int qa = (act[g] ? qg[g] : 0) + (lane & 31);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) gload16(qf[g][ks], qb_ + (int64_t)qa * ld + 16 * ks + 8 * (lane >> 5));
+            if constexpr (SEG) {
+                gload4(ssw[g], seg_start + boff + qa);
+                gload4(sew[g], seg_end + boff + qa);
+            }
         }
         if constexpr (DROP) gload4s(mw[g], mrow[g], loff);
     }
     const int qlast = (Q0 + 255 < T - 1) ? Q0 + 255 : T - 1;
     const int nkv = qlast / 64 + 1;
-    const int npipe = act[1] ? (qg[1] + 31) / 64 : 0;   // B's diagonal tile: first unpipelined tile
+    const int npipe = SEG ? 0 : (act[1] ? (qg[1] + 31) / 64 : 0);   // B's diagonal tile: first unpipelined tile
     {   // the V half of tile -1's slot is the pipeline head's "previous tile": zeros
         const int r = tid >> 3, c = tid & 7;
         *(uint4*)(slot(-1) + TILE + aoff(r, c)) = make_uint4(0, 0, 0, 0);
@@ -408,8 +481,20 @@ __device__ __forceinline__ void fwd_qblock_dma(int qblk, int bh, char* smem, int
             for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qf[g][ks]));
         }
         asm volatile("" : "+v"(mw[g]));
+        if constexpr (SEG) asm volatile("" : "+v"(ssw[g]), "+v"(sew[g]));
     }
     if constexpr (!DROP) mw[0] = mw[1] = 0u;
+    int ss[2] = {0, 0};
+    uint32_t peers[2] = {0u, 0u};
+    if constexpr (SEG) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            if (!act[g]) continue;
+            const int qa = qg[g] + (lane & 31);
+            ss[g] = seg_lo(ssw[g], qa);
+            peers[g] = seg_peers(ss[g], seg_hi(sew[g], qa), qg[g]);
+        }
+    }
     auto qk = [&](fv16 (&s)[2], const char* Ki, int g) {
         if constexpr (QR) qk_tile_reg(s, Ki, qf[g], lane);
         else qk_tile(s, Ki, Qimg, qr[g], lane);
@@ -478,15 +563,19 @@ __device__ __forceinline__ void fwd_qblock_dma(int qblk, int bh, char* smem, int
             if (!act[g] || k0 > qg[g] + 31) continue;
             const int rel = __builtin_amdgcn_readfirstlane(qg[g] - k0);
             if constexpr (QR) {
+                const int srel = SEG ? ss[g] - k0 : 0;
+                if constexpr (SEG) {
+                    if (__all(srel >= 64)) continue;   // the tile precedes every lane's segment
+                }
                 if (rel >= 64)
-                    fwd_group_tile<DROP, 2, -1, true>(Ki, Vi, nullptr, 0, lane, scale_log2, m_run[g], l_run[g],
-                                                      oacc[g], mw[g], ones, qf[g]);
+                    fwd_group_tile<DROP, 2, -1, true, SEG>(Ki, Vi, nullptr, 0, lane, scale_log2, m_run[g], l_run[g],
+                                                           oacc[g], mw[g], ones, qf[g], srel, peers[g]);
                 else if (rel == 32)
-                    fwd_group_tile<DROP, 2, 1, true>(Ki, Vi, nullptr, 0, lane, scale_log2, m_run[g], l_run[g],
-                                                     oacc[g], mw[g], ones, qf[g]);
+                    fwd_group_tile<DROP, 2, 1, true, SEG>(Ki, Vi, nullptr, 0, lane, scale_log2, m_run[g], l_run[g],
+                                                          oacc[g], mw[g], ones, qf[g], srel, peers[g]);
                 else
-                    fwd_group_tile<DROP, 1, 0, true>(Ki, Vi, nullptr, 0, lane, scale_log2, m_run[g], l_run[g],
-                                                     oacc[g], mw[g], ones, qf[g]);
+                    fwd_group_tile<DROP, 1, 0, true, SEG>(Ki, Vi, nullptr, 0, lane, scale_log2, m_run[g], l_run[g],
+                                                          oacc[g], mw[g], ones, qf[g], srel, peers[g]);
             } else {
                 if (rel >= 64)
                     fwd_group_tile<DROP, 2, -1>(Ki, Vi, Qimg, qr[g], lane, scale_log2, m_run[g], l_run[g], oacc[g],
@@ -530,6 +619,28 @@ __global__ __launch_bounds__(256, 2) void k_attn_fwd_d64d(int64_t T_, int H, con
         if (pass) __syncthreads();
         fwd_qblock_dma<DROP, QR>(pass ? x : first, bh, smem, T_, H, q, k, v, ld, o, ldo, lse, scale_log2, mask,
                                  dscale);
+    }
+}
+
+template <bool DROP>
+__global__ __launch_bounds__(256, 2) void k_attn_fwd_d64d_seg(int64_t T_, int H, const bf16_t* __restrict__ q,
+                                                              const bf16_t* __restrict__ k,
+                                                              const bf16_t* __restrict__ v, int64_t ld,
+                                                              bf16_t* __restrict__ o, int64_t ldo,
+                                                              float* __restrict__ lse, float scale_log2,
+                                                              const uint32_t* __restrict__ mask, float dscale,
+                                                              const int32_t* __restrict__ seg_start,
+                                                              const int32_t* __restrict__ seg_end) {
+    __shared__ __attribute__((aligned(16))) char smem[FwdRing<true>::LDS];
+    int x, bh;
+    block_coords<false>(x, bh);
+    const int nq = (int)((T_ + 255) / 256), first = nq - 1 - x;
+    const int npass = x == first ? 1 : 2;
+#pragma unroll 1
+    for (int pass = 0; pass < npass; ++pass) {
+        if (pass) __syncthreads();
+        fwd_qblock_dma<DROP, true, true>(pass ? x : first, bh, smem, T_, H, q, k, v, ld, o, ldo, lse, scale_log2, mask,
+                                         dscale, seg_start, seg_end);
     }
 }
 

@@ -130,6 +130,42 @@ __device__ __forceinline__ void mask_upper(fv16& x, int qa, int key0, int lane, 
         if ((r & 3) + 8 * (r >> 2) > rel) x[r] = fill;
 }
 
+// ---- packed rows (the SEG instantiations): query i sees key j iff seg_start[i] <= j <= i ------------
+// Forward / dQ orientation (column = query): rows whose key, key0 + acc_row(r), lies before the
+// lane's segment start become -inf -- the mirror of mask_upper; rel = seg_start - key0.  Called
+// under a wave-uniform branch (some lane's segment starts inside or after the subtile).
+__device__ __forceinline__ void mask_before(fv16& x, int rel, int lane) {
+    const int lim = rel - 4 * (lane >> 5);
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if ((r & 3) + 8 * (r >> 2) < lim) x[r] = -INFINITY;
+}
+// dK/dV orientation (column = key): rows whose query, q0 + acc_row(r), lies at or beyond the lane's
+// segment end become -inf; rel = seg_end - q0
+__device__ __forceinline__ void mask_from(fv16& x, int rel, int lane) {
+    const int lim = rel - 4 * (lane >> 5);
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if ((r & 3) + 8 * (r >> 2) >= lim) x[r] = -INFINITY;
+}
+// seg_start / seg_end of this lane's row as loaded, made safe: 0 <= start <= row < end (a malformed
+// bound then still leaves every query its own key, so no softmax row is empty)
+__device__ __forceinline__ int seg_lo(uint32_t w, int row) {
+    const int s = (int)w;
+    return s < 0 ? 0 : (s > row ? row : s);
+}
+__device__ __forceinline__ int seg_hi(uint32_t w, int row) {
+    const int e = (int)w;
+    return e <= row ? row + 1 : e;
+}
+// the lanes (as query bits 0..31 of a 32-query group starting at qg) of this lane's segment [lo, hi)
+__device__ __forceinline__ uint32_t seg_peers(int lo, int hi, int qg) {
+    const int a = lo - qg, b = hi - qg;
+    const uint32_t below_b = b >= 32 ? 0xffffffffu : (1u << b) - 1u;
+    const uint32_t below_a = a <= 0 ? 0u : (1u << a) - 1u;
+    return below_b & ~below_a;
+}
+
 // XCD-aware block order for a (row blocks, B*H) grid: the dispatcher deals linear block ids to the
 // 8 XCDs round-robin and each XCD has its own L2; the bijective remap hands every XCD a contiguous
 // run of logical ids (whole (b, h) groups, which stream the same K/V or Q/dO), measured 35 -> 81 %
@@ -257,6 +293,25 @@ __device__ __forceinline__ void rescale_if(float mt, float& m_run, fv4& l_run, f
     }
 }
 
+// The same for packed rows.  rescale_if moves the running max of EVERY lane once any lane of the wave
+// asks for it, so a query's rounding would depend on the other segments that share its wave.  Here a
+// lane moves iff a lane of its own segment asks (peers: seg_peers; lanes l and l + 32 hold the same
+// query and vote alike), which is rescale_if itself when the wave holds one segment.  A lane whose
+// keys so far were all masked has mt = -inf and m_run = -FLT_MAX: it never asks, and moved by a peer
+// it keeps m_run (alpha = exp2(0)), so no exp2(-inf - -inf) arises.
+__device__ __forceinline__ void rescale_if_seg(float mt, float& m_run, fv4& l_run, fv16 (&o)[2], uint32_t peers) {
+    const uint64_t ask = __ballot(mt > m_run + RESCALE_THR);
+    if (ask) {
+        const bool move = (((uint32_t)ask | (uint32_t)(ask >> 32)) & peers) != 0;
+        const float mn = move ? fmaxf(m_run, mt) : m_run;
+        const float alpha = __builtin_amdgcn_exp2f(m_run - mn);
+        o[0] *= alpha;
+        o[1] *= alpha;
+        l_run *= alpha;
+        m_run = mn;
+    }
+}
+
 // low / high 16 bits all-ones where bit j / j + 16 of a FWD keep word is set: v_lshlrev_b32 puts them
 // at bits 15 / 31, v_perm_b32 selectors 8 / 9 replicate those bits over bytes 0-1 / 2-3
 __device__ __forceinline__ uint32_t pair_mask(uint32_t w, int j) {
@@ -316,10 +371,13 @@ __device__ __forceinline__ void pv_tile(fv16 (&o)[2], const char* Vi, const sv8 
 // lies wholly above the diagonal); DIAG = the subtile holding the diagonal (-1: none) -- the only
 // one masked.  Straight-line code per case (the merged form copied accumulators between paths).
 // QREG: the group's Q fragments come from registers (qreg[4]) instead of the Q image.
-template <bool DROP, int NSUB, int DIAG, bool QREG = false>
+// SEG (packed rows): srel = the lane's segment start relative to the tile's first key, peers = the
+// lanes of its segment (seg_peers); subtiles that begin before some lane's segment are masked below it.
+template <bool DROP, int NSUB, int DIAG, bool QREG = false, bool SEG = false>
 __device__ __forceinline__ void fwd_group_tile(const char* Ki, const char* Vi, const char* Qimg, int qr, int lane,
                                                float scale_log2, float& m_run, fv4& l_run, fv16 (&o)[2],
-                                               uint32_t mw, const sv8& ones, const sv8* qreg = nullptr) {
+                                               uint32_t mw, const sv8& ones, const sv8* qreg = nullptr, int srel = 0,
+                                               uint32_t peers = 0u) {
     fv16 s[2];
     s[0] = fv16{};
     s[1] = fv16{};
@@ -330,7 +388,14 @@ __device__ __forceinline__ void fwd_group_tile(const char* Ki, const char* Vi, c
         if (NSUB == 2) s[1] = mfma32(frag_row(Ki, 32, ks, lane), qf, s[1]);
     }
     if (DIAG >= 0) mask_upper(s[DIAG], lane & 31, 0, lane, -INFINITY);   // key0 = the group's first query
-    rescale_if(tile_max<NSUB>(s) * scale_log2, m_run, l_run, o);
+    if constexpr (SEG) {
+#pragma unroll
+        for (int kt = 0; kt < NSUB; ++kt)
+            if (__any(srel > 32 * kt)) mask_before(s[kt], srel - 32 * kt, lane);
+        rescale_if_seg(tile_max<NSUB>(s) * scale_log2, m_run, l_run, o, peers);
+    } else {
+        rescale_if(tile_max<NSUB>(s) * scale_log2, m_run, l_run, o);
+    }
     sv8 pf[2][2];
     softmax_pack<DROP, NSUB>(s, scale_log2, m_run, l_run, mw, pf, ones);
     pv_tile<NSUB>(o, Vi, pf, lane);
@@ -343,13 +408,18 @@ __device__ __forceinline__ void fwd_group_tile(const char* Ki, const char* Vi, c
 // =====================================================================================
 // one 64-key tile (K / V images, first key k0) of a dQ query group starting at query qg: its 32-key
 // subtiles up to the diagonal; only the subtile whose first key is qg holds the diagonal
-template <bool DROP>
+// SEG (packed rows): ss = the lane's segment start; subtiles wholly before every lane's segment are
+// skipped, those that begin before some lane's are masked below it (P = exp2(-inf) = 0 there)
+template <bool DROP, bool SEG = false>
 __device__ __forceinline__ void dq_group_tile(const char* Ki, const char* Vi, int k0, int qg, const sv8 (&qf)[4],
                                               const sv8 (&df)[4], float lse2, float dl, uint32_t mw, float c2,
-                                              fv16 (&dqa)[2], int lane) {
+                                              fv16 (&dqa)[2], int lane, int ss = 0) {
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
         if (k0 + 32 * kt > qg + 31) break;   // subtile fully masked
+        if constexpr (SEG) {
+            if (__all(ss >= k0 + 32 * kt + 32)) continue;
+        }
         const bool diag = __builtin_amdgcn_readfirstlane(k0 + 32 * kt == qg);
         // dP^T starts from -delta' (its column's, lane-uniform), so the chain leaves dP - delta'
         fv16 s = fv16{}, dp = fv16{} + dl;
@@ -359,6 +429,9 @@ __device__ __forceinline__ void dq_group_tile(const char* Ki, const char* Vi, in
             dp = mfma32(frag_row(Vi, 32 * kt, ks, lane), df[ks], dp);
         }
         if (diag) mask_upper(s, lane & 31, 0, lane, -INFINITY);
+        if constexpr (SEG) {
+            if (__any(ss > k0 + 32 * kt)) mask_before(s, ss - (k0 + 32 * kt), lane);
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float p = __builtin_amdgcn_exp2f(fmaf(s[r], c2, -lse2));
@@ -380,14 +453,19 @@ __device__ __forceinline__ void dq_group_tile(const char* Ki, const char* Vi, in
 // =====================================================================================
 // one 64-query tile (Q / dO images, their lse*log2e and -delta' rows) of a dK/dV key group starting
 // at key kq (key = kq + (lane & 31)): the 32-query subtiles that reach the group's keys
-template <bool DROP>
+// SEG (packed rows): se = the end (exclusive) of the segment of the lane's key; subtiles at or beyond
+// every lane's segment end are skipped, those that reach past some lane's are masked from it on
+template <bool DROP, bool SEG = false>
 __device__ __forceinline__ void dkdv_tile(const char* Qi, const char* Oi, const float* st_lse, const float* st_del,
                                           int q0, int kq, int key, const sv8 (&kf)[4], const sv8 (&vf)[4], uint32_t mw,
-                                          float c2, fv16 (&dka)[2], fv16 (&dva)[2], int lane) {
+                                          float c2, fv16 (&dka)[2], fv16 (&dva)[2], int lane, int se = 0) {
 #pragma unroll
     for (int qs = 0; qs < 2; ++qs) {
         const int q0s = q0 + 32 * qs;
         if (q0s + 31 < kq) continue;   // every query of the subtile precedes every key
+        if constexpr (SEG) {
+            if (__all(se <= q0s)) continue;
+        }
         // dP starts from -delta' of its rows (the accumulator's initial value), so the MFMA
         // chain leaves dP - delta'; dS = 1/(1-p) P (keep dP - delta'), the 1/(1-p) in the epilogue
         fv16 s = fv16{}, dp;
@@ -410,6 +488,9 @@ __device__ __forceinline__ void dkdv_tile(const char* Qi, const char* Oi, const 
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if ((r & 3) + 8 * (r >> 2) < rel) s[r] = -INFINITY;
+        }
+        if constexpr (SEG) {
+            if (__any(se < q0s + 32)) mask_from(s, se - q0s, lane);
         }
         fv16 z;
 #pragma unroll

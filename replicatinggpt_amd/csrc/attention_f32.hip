@@ -19,11 +19,13 @@ __device__ __forceinline__ fv4 mfma_f32x4(float a, float b, fv4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-template <int DP4>  // D padded to a multiple of 4 (<= 32)
-__global__ __launch_bounds__(256) void k_attn_fwd_f32mfma(int64_t T_, int H, int D, const float* __restrict__ q,
-                                                          const float* __restrict__ k, const float* __restrict__ v,
-                                                          int64_t ld, float* __restrict__ o, int64_t ldo,
-                                                          float* __restrict__ lse, float scale) {
+// SEG (packed rows, k_attn_fwd_f32mfma_seg): keys before the lane's query's segment start are masked
+// as well; a 64-key tile wholly masked for a query leaves its statistics alone (m_new == -inf guards).
+template <int DP4, bool SEG>  // D padded to a multiple of 4 (<= 32)
+__device__ __forceinline__ void fwd_f32mfma(int64_t T_, int H, int D, const float* __restrict__ q,
+                                            const float* __restrict__ k, const float* __restrict__ v, int64_t ld,
+                                            float* __restrict__ o, int64_t ldo, float* __restrict__ lse, float scale,
+                                            const int32_t* __restrict__ seg_start) {
     constexpr int KS = DP4 / 4;           // k-steps of S^T
     constexpr int KLD = DP4 + 1, VLD = 33;
     __shared__ float Ks[64 * KLD];
@@ -42,6 +44,13 @@ __global__ __launch_bounds__(256) void k_attn_fwd_f32mfma(int64_t T_, int H, int
     for (int t = 0; t < KS; ++t) {
         const int e = 4 * t + g;
         qf[t] = (qa < T_ && e < D) ? qb[qa * ld + e] : 0.f;
+    }
+    int64_t ss = 0;   // SEG: the first key this lane's query sees, clamped into [0, qa]
+    if constexpr (SEG) {
+        if (qa < T_) {
+            ss = seg_start[(int64_t)b * T_ + qa];
+            ss = ss < 0 ? 0 : (ss > qa ? qa : ss);
+        }
     }
     fv4 oacc[2] = {fv4{0.f, 0.f, 0.f, 0.f}, fv4{0.f, 0.f, 0.f, 0.f}};
     float m_run = -INFINITY, l_run = 0.f;
@@ -76,6 +85,9 @@ __global__ __launch_bounds__(256) void k_attn_fwd_f32mfma(int64_t T_, int H, int
                 const int64_t key = k0 + 16 * kt + 4 * g + r;
                 float x = st[kt][r] * scale;
                 if (key > qa || key >= T_) x = -INFINITY;
+                if constexpr (SEG) {
+                    if (key < ss) x = -INFINITY;
+                }
                 st[kt][r] = x;
                 mx = fmaxf(mx, x);
             }
@@ -120,6 +132,24 @@ __global__ __launch_bounds__(256) void k_attn_fwd_f32mfma(int64_t T_, int H, int
             if (e < D) orow[e] = oacc[et][r] * inv;
         }
     if (g == 0) lse[(int64_t)bh * T_ + qa] = m_run + logf(l_run);
+}
+
+template <int DP4>
+__global__ __launch_bounds__(256) void k_attn_fwd_f32mfma(int64_t T_, int H, int D, const float* __restrict__ q,
+                                                          const float* __restrict__ k, const float* __restrict__ v,
+                                                          int64_t ld, float* __restrict__ o, int64_t ldo,
+                                                          float* __restrict__ lse, float scale) {
+    fwd_f32mfma<DP4, false>(T_, H, D, q, k, v, ld, o, ldo, lse, scale, nullptr);
+}
+
+template <int DP4>
+__global__ __launch_bounds__(256) void k_attn_fwd_f32mfma_seg(int64_t T_, int H, int D, const float* __restrict__ q,
+                                                              const float* __restrict__ k,
+                                                              const float* __restrict__ v, int64_t ld,
+                                                              float* __restrict__ o, int64_t ldo,
+                                                              float* __restrict__ lse, float scale,
+                                                              const int32_t* __restrict__ seg_start) {
+    fwd_f32mfma<DP4, true>(T_, H, D, q, k, v, ld, o, ldo, lse, scale, seg_start);
 }
 
 // Sequence-resident form of k_attn_fwd_f32mfma for T <= 256 (the generate() window and the fp32
@@ -319,6 +349,15 @@ void launch_fwd_f32(int64_t B, int64_t T, int H, int D, const float* q, const fl
         else
             k_attn_fwd_f32mfma<decltype(dp)::value><<<dim3(ceil_div(T, 64), (unsigned)(B * H)), 256, 0, st>>>(
                 T, H, D, q, k, v, ld, o, ldo, lse, scale);
+    });
+}
+// packed rows: the 64-query-block kernel at every T (the sequence-resident form, bitwise its equal,
+// takes no mask), so an all-zero seg_start gives launch_fwd_f32's bits
+void launch_fwd_f32_seg(int64_t B, int64_t T, int H, int D, const float* q, const float* k, const float* v, int64_t ld,
+                        float* o, int64_t ldo, float* lse, float scale, const int32_t* seg_start, hipStream_t st) {
+    with_dp4(D, [&](auto dp) {
+        k_attn_fwd_f32mfma_seg<decltype(dp)::value><<<dim3(ceil_div(T, 64), (unsigned)(B * H)), 256, 0, st>>>(
+            T, H, D, q, k, v, ld, o, ldo, lse, scale, seg_start);
     });
 }
 }  // namespace attn

@@ -38,11 +38,24 @@ __device__ __forceinline__ void load_rows(float* dst, int DP, const T* base, int
     }
 }
 
-template <typename T>
+// SEG: packed rows -- query i sees key j iff seg_start[b, i] <= j <= i (seg_lo / seg_hi below clamp a
+// malformed bound so that every query still sees itself); the dK/dV kernel reads the same mask from
+// the key's side, seg_end[b, j] > i.
+__device__ __forceinline__ int64_t seg_lo(const int32_t* seg_start, int64_t row, int64_t qa) {
+    const int64_t s = seg_start[row];
+    return s < 0 ? 0 : (s > qa ? qa : s);
+}
+__device__ __forceinline__ int64_t seg_hi(const int32_t* seg_end, int64_t row, int64_t ka, int64_t T_) {
+    const int64_t e = seg_end[row];
+    return e <= ka ? ka + 1 : (e > T_ ? T_ : e);
+}
+
+template <typename T, bool SEG>
 __global__ __launch_bounds__(256) void k_attn_fwd_generic(int64_t T_, int H, int D, const T* __restrict__ q,
                                                           const T* __restrict__ k, const T* __restrict__ v, int64_t ld,
                                                           T* __restrict__ o, int64_t ldo, float* __restrict__ lse,
-                                                          float scale, DropArgs drop) {
+                                                          float scale, DropArgs drop,
+                                                          const int32_t* __restrict__ seg_start) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int DP = D + 1;
     float* Qs = sm;
@@ -58,6 +71,8 @@ __global__ __launch_bounds__(256) void k_attn_fwd_generic(int64_t T_, int H, int
     const T* kbase = k + (int64_t)b * T_ * ld + h * D;
     const T* vbase = v + (int64_t)b * T_ * ld + h * D;
     load_rows<T>(Qs, DP, qbase, ld, q0, T_, D, tid);
+    int64_t ss = 0;
+    if constexpr (SEG) ss = qa < T_ ? seg_lo(seg_start, (int64_t)b * T_ + qa, qa) : 0;
     const uint64_t stream = drop.thr ? dropout_stream(drop.rng_call, drop.site) : 0;
     float m_run = -INFINITY, l_run = 0.f;
     float oacc[16];
@@ -78,6 +93,9 @@ __global__ __launch_bounds__(256) void k_attn_fwd_generic(int64_t T_, int H, int
             for (int e = 0; e < D; ++e) acc += Qs[qi * DP + e] * Ks[j * DP + e];
             acc *= scale;
             if (key > qa || key >= T_) acc = -INFINITY;
+            if constexpr (SEG) {
+                if (key < ss) acc = -INFINITY;
+            }
             s[jj] = acc;
             mx = fmaxf(mx, acc);
         }
@@ -155,13 +173,14 @@ __global__ void k_attn_delta(int64_t B, int64_t T_, int H, int D, const T* __res
     delta[(b * H + h) * T_ + t] = s;
 }
 
-template <typename T>
+template <typename T, bool SEG>
 __global__ __launch_bounds__(256) void k_attn_dq_generic(int64_t T_, int H, int D, const T* __restrict__ q,
                                                          const T* __restrict__ k, const T* __restrict__ v, int64_t ld,
                                                          const T* __restrict__ dout, int64_t ldd,
                                                          const float* __restrict__ lse,
                                                          const float* __restrict__ delta, T* __restrict__ dq,
-                                                         int64_t lddq, float scale, DropArgs drop) {
+                                                         int64_t lddq, float scale, DropArgs drop,
+                                                         const int32_t* __restrict__ seg_start) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int DP = D + 1;
     float* Qs = sm;
@@ -180,6 +199,8 @@ __global__ __launch_bounds__(256) void k_attn_dq_generic(int64_t T_, int H, int 
     const bool valid_q = qa < T_;
     const float lq = valid_q ? lse[(int64_t)bh * T_ + qa] : 0.f;
     const float dq_ = valid_q ? delta[(int64_t)bh * T_ + qa] : 0.f;
+    int64_t ss = 0;
+    if constexpr (SEG) ss = valid_q ? seg_lo(seg_start, boff + qa, qa) : 0;
     const uint64_t stream = drop.thr ? dropout_stream(drop.rng_call, drop.site) : 0;
     float acc[16];
 #pragma unroll
@@ -195,7 +216,7 @@ __global__ __launch_bounds__(256) void k_attn_dq_generic(int64_t T_, int H, int 
             const int j = sub + 8 * jj;
             const int64_t key = k0 + j;
             float ds = 0.f;
-            if (valid_q && key <= qa) {
+            if (valid_q && key <= qa && (!SEG || key >= ss)) {
                 float s = 0.f, dp = 0.f;
                 for (int e = 0; e < D; ++e) {
                     s += Qs[qi * DP + e] * Ks[j * DP + e];
@@ -231,14 +252,14 @@ __global__ __launch_bounds__(256) void k_attn_dq_generic(int64_t T_, int H, int 
     }
 }
 
-template <typename T>
+template <typename T, bool SEG>
 __global__ __launch_bounds__(256) void k_attn_dkdv_generic(int64_t T_, int H, int D, const T* __restrict__ q,
                                                            const T* __restrict__ k, const T* __restrict__ v,
                                                            int64_t ld, const T* __restrict__ dout, int64_t ldd,
                                                            const float* __restrict__ lse,
                                                            const float* __restrict__ delta, T* __restrict__ dk,
                                                            T* __restrict__ dv, int64_t lddkv, float scale,
-                                                           DropArgs drop) {
+                                                           DropArgs drop, const int32_t* __restrict__ seg_end) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int DP = D + 1;
     float* Ks = sm;
@@ -256,6 +277,8 @@ __global__ __launch_bounds__(256) void k_attn_dkdv_generic(int64_t T_, int H, in
     const int64_t boff = (int64_t)b * T_;
     load_rows<T>(Ks, DP, k + boff * ld + h * D, ld, k0, T_, D, tid);
     load_rows<T>(Vs, DP, v + boff * ld + h * D, ld, k0, T_, D, tid);
+    int64_t se = T_;
+    if constexpr (SEG) se = ka < T_ ? seg_hi(seg_end, boff + ka, ka, T_) : T_;
     const uint64_t stream = drop.thr ? dropout_stream(drop.rng_call, drop.site) : 0;
     float adk[16], adv[16];
 #pragma unroll
@@ -277,7 +300,7 @@ __global__ __launch_bounds__(256) void k_attn_dkdv_generic(int64_t T_, int H, in
             const int qi = sub + 8 * ii;
             const int64_t qa = q0 + qi;
             float z = 0.f, ds = 0.f;
-            if (ka < T_ && qa < T_ && ka <= qa) {
+            if (ka < T_ && qa < T_ && ka <= qa && (!SEG || qa < se)) {
                 float s = 0.f, dp = 0.f;
                 for (int e = 0; e < D; ++e) {
                     s += Ks[kj * DP + e] * Qs[qi * DP + e];
@@ -341,28 +364,34 @@ void with_dtype(int dtype, F&& f) {
 namespace cg {
 namespace attn {
 void launch_fwd_generic(int dtype, int64_t B, int64_t T_, int H, int D, const void* q, const void* k, const void* v,
-                        int64_t ld, void* o, int64_t ldo, float* lse, float scale, const DropArgs& d, hipStream_t st) {
+                        int64_t ld, void* o, int64_t ldo, float* lse, float scale, const DropArgs& d, hipStream_t st,
+                        const int32_t* seg_start) {
     const dim3 grid(ceil_div(T_, GB), (unsigned)(B * H));
     with_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        k_attn_fwd_generic<T><<<grid, 256, generic_lds<float>(D, 3, 1), st>>>(
-            T_, H, D, (const T*)q, (const T*)k, (const T*)v, ld, (T*)o, ldo, lse, scale, d);
+        with_flag(seg_start != nullptr, [&](auto seg) {
+            k_attn_fwd_generic<T, decltype(seg)::value><<<grid, 256, generic_lds<float>(D, 3, 1), st>>>(
+                T_, H, D, (const T*)q, (const T*)k, (const T*)v, ld, (T*)o, ldo, lse, scale, d, seg_start);
+        });
     });
 }
 
 void launch_bwd_generic(int dtype, int64_t B, int64_t T_, int H, int D, const void* q, const void* k, const void* v,
                         int64_t ld, const void* o, int64_t ldo, const void* dout, int64_t ldd, const float* lse,
                         float* delta, void* dq, void* dk, void* dv, int64_t lddqkv, float scale, const DropArgs& d,
-                        hipStream_t st) {
+                        hipStream_t st, const int32_t* seg_start, const int32_t* seg_end) {
     const dim3 grid(ceil_div(T_, GB), (unsigned)(B * H));
     with_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         const T *Q = (const T*)q, *K = (const T*)k, *V = (const T*)v, *DO = (const T*)dout;
         k_attn_delta<T><<<ceil_div(B * T_ * H, 256), 256, 0, st>>>(B, T_, H, D, (const T*)o, ldo, DO, ldd, delta);
-        k_attn_dq_generic<T><<<grid, 256, generic_lds<float>(D, 4, 1), st>>>(T_, H, D, Q, K, V, ld, DO, ldd, lse, delta,
-                                                                             (T*)dq, lddqkv, scale, d);
-        k_attn_dkdv_generic<T><<<grid, 256, generic_lds<float>(D, 4, 2), st>>>(T_, H, D, Q, K, V, ld, DO, ldd, lse, delta,
-                                                                               (T*)dk, (T*)dv, lddqkv, scale, d);
+        with_flag(seg_start != nullptr, [&](auto seg) {
+            constexpr bool SEG = decltype(seg)::value;
+            k_attn_dq_generic<T, SEG><<<grid, 256, generic_lds<float>(D, 4, 1), st>>>(
+                T_, H, D, Q, K, V, ld, DO, ldd, lse, delta, (T*)dq, lddqkv, scale, d, seg_start);
+            k_attn_dkdv_generic<T, SEG><<<grid, 256, generic_lds<float>(D, 4, 2), st>>>(
+                T_, H, D, Q, K, V, ld, DO, ldd, lse, delta, (T*)dk, (T*)dv, lddqkv, scale, d, seg_end);
+        });
     });
 }
 }  // namespace attn

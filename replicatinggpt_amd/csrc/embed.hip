@@ -349,3 +349,84 @@ extern "C" int cg_embed_bwd(const int64_t* idx, const float* dx, float* dwte, fl
     CG_LAUNCH_CHECK("cg_embed_bwd");
     return CG_OK;
 }
+
+// ---- packed rows: positions restart at each segment ---------------------------------------
+// x[b,t,:] = wte[idx[b,t],:] + wpe[t - seg_start[b,t],:], the position clamped into [0, T) so that a
+// malformed seg_start reads inside wpe.  One block per (b, t) row, 16-B columns where C allows.
+__global__ __launch_bounds__(128) void k_embed_fwd_seg(const int64_t* __restrict__ idx,
+                                                       const int32_t* __restrict__ seg_start,
+                                                       const float* __restrict__ wte, const float* __restrict__ wpe,
+                                                       float* __restrict__ x, int64_t T, int64_t C, int64_t V, int vec4) {
+    const int64_t row = blockIdx.x;
+    const int64_t t = row % T;
+    int64_t tok = idx[row];
+    tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
+    int64_t pos = t - (int64_t)seg_start[row];
+    pos = pos < 0 ? 0 : (pos >= T ? T - 1 : pos);
+    const float* a = wte + tok * C;
+    const float* p = wpe + pos * C;
+    float* o = x + row * C;
+    if (vec4) {
+        for (int64_t c = threadIdx.x * 4; c < C; c += blockDim.x * 4) {
+            const float4 u = *(const float4*)(a + c), w = *(const float4*)(p + c);
+            *(float4*)(o + c) = make_float4(u.x + w.x, u.y + w.y, u.z + w.z, u.w + w.w);
+        }
+    } else {
+        for (int64_t c = threadIdx.x; c < C; c += blockDim.x) o[c] = a[c] + p[c];
+    }
+}
+
+// dwpe[p,c] (=|+=) sum of dx[b,t,c] over the positions t = s + p of every segment [s, e) with s + p < e,
+// in (b, segment) order: one thread per (p, c) walks each row's segments through seg_end (e clamped into
+// (s, T], so a malformed seg_end neither stalls the walk nor leaves the row).  No atomics: bitwise
+// reproducible.  Any T (the token histogram of k_embed_bwd_tok_partial would stop at 640 positions).
+__global__ __launch_bounds__(256) void k_embed_bwd_pos_seg(const float* __restrict__ dx,
+                                                           const int32_t* __restrict__ seg_end,
+                                                           float* __restrict__ dwpe, int64_t B, int64_t T, int64_t C,
+                                                           int accumulate) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= T * C) return;
+    const int64_t p = i / C, c = i - p * C;
+    float sum = 0.f;
+    for (int64_t b = 0; b < B; ++b) {
+        const int32_t* se = seg_end + b * T;
+        const float* d = dx + b * T * C + c;
+        int64_t s = 0;
+        while (s < T) {
+            int64_t e = se[s];
+            e = e <= s ? s + 1 : (e > T ? T : e);
+            if (s + p < e) sum += d[(s + p) * C];
+            s = e;
+        }
+    }
+    dwpe[i] = accumulate ? dwpe[i] + sum : sum;
+}
+
+extern "C" int cg_embed_fwd_seg(const int64_t* idx, const int32_t* seg_start, const float* wte, const float* wpe,
+                                float* x, int64_t B, int64_t T, int64_t C, int64_t V, void* stream) {
+    CG_REQUIRE(B > 0 && T > 0 && C > 0 && V > 0, "cg_embed_fwd_seg: bad shape");
+    CG_REQUIRE(seg_start, "cg_embed_fwd_seg: seg_start is required");
+    const bool al16 = ((((uintptr_t)wte) | ((uintptr_t)wpe) | ((uintptr_t)x)) & 15) == 0;
+    k_embed_fwd_seg<<<(unsigned)(B * T), 128, 0, (hipStream_t)stream>>>(idx, seg_start, wte, wpe, x, T, C, V,
+                                                                        C % 4 == 0 && al16);
+    CG_LAUNCH_CHECK("cg_embed_fwd_seg");
+    return CG_OK;
+}
+
+extern "C" int cg_embed_bwd_seg(const int64_t* idx, const int32_t* seg_end, const float* dx, float* dwte, float* dwpe,
+                                int64_t B, int64_t T, int64_t C, int64_t V, int accumulate, void* workspace,
+                                void* stream) {
+    CG_REQUIRE(B > 0 && T > 0 && C > 0 && V > 0, "cg_embed_bwd_seg: bad shape");
+    CG_REQUIRE(seg_end, "cg_embed_bwd_seg: seg_end is required");
+    // the token gradient does not depend on the positions: cg_embed_bwd's kernels, same bits
+    if (dwte) {
+        const int rc = cg_embed_bwd(idx, dx, dwte, nullptr, B, T, C, V, accumulate, workspace, stream);
+        if (rc != CG_OK) return rc;
+    }
+    if (dwpe) {
+        k_embed_bwd_pos_seg<<<ceil_div(T * C, 256), 256, 0, (hipStream_t)stream>>>(dx, seg_end, dwpe, B, T, C,
+                                                                                   accumulate);
+        CG_LAUNCH_CHECK("cg_embed_bwd_seg");
+    }
+    return CG_OK;
+}

@@ -210,3 +210,132 @@ class PairSampler:
         ops.gather_pairs(self.table_dev, self.plen_dev, self.tlen_dev, ix_dev, x, y, self.pad_token,
                          self.ignore_index)
         return x, y
+
+
+def first_fit(lengths, order, capacity):
+    """First-fit packing: the items, taken in ``order``, each go into the first row that still has
+    room for their length, else into a new row.  Returns the rows as lists of item indices."""
+    rows, room = [], []
+    for n in order:
+        need = int(lengths[n])
+        for r, free in enumerate(room):
+            if need <= free:
+                rows[r].append(int(n))
+                room[r] -= need
+                break
+        else:
+            rows.append([int(n)])
+            room.append(capacity - need)
+    return rows
+
+
+class PackedPairSampler:
+    """get_batch over (prompt, completion) pairs with several pairs per row (DESIGN.md §4 "Packed
+    rows").  A pair takes ``tlen - 1`` input positions (its packed row without the last token, as
+    PairSampler's x); a row is a concatenation of such segments and, where they leave room, a tail of
+    ``pad_token``.  get_batch returns (x, y, seg_start): seg_start[b, t] (int32) is the index of the
+    first token of the segment that holds position t, the padding tail being a segment of its own.
+    y[b, j] is the next token where that token belongs to the segment's completion and
+    ``ignore_index`` elsewhere -- PairSampler's rule per segment, so no target crosses a segment's end
+    -- and ``ignore_index`` on the padding.
+
+    The pairs are split 90/10 as PairSampler's rows; each split's pairs are shuffled with
+    ``generator`` (train first, then val) and packed first-fit into rows of capacity ``block_size``;
+    ``repack()`` reshuffles and repacks.  get_batch draws B*W packed-row indices of the split on the
+    CPU generator, every rank the same ones, and keeps its own slice, as the other samplers do."""
+
+    ignore_index = -100
+    packed = True
+
+    def __init__(self, pairs, block_size, batch_size, world_size=1, rank=0, generator=None, pad_token=0,
+                 device=None):
+        self.T = block_size
+        self.B = batch_size
+        self.W = world_size
+        self.rank = rank
+        self.generator = generator
+        self.pad_token = int(pad_token)
+        self.table_cpu, self.plen_cpu, self.tlen_cpu = pack_pairs(pairs, block_size)
+        self.n = int(0.9 * len(pairs))      # pairs [0, n) train, [n, N) val
+        self.device = None
+        self._dev = {}
+        self._ring = None
+        self._ring_i = 0
+        self.repack()
+        if device is not None:
+            self.to(device)
+
+    def _build(self, lo, n):
+        """Shuffle pairs lo .. lo+n-1 and pack them: (x, y, seg_start) tables [rows, T] and the rows."""
+        T = self.T
+        order = (torch.randperm(n, generator=self.generator) + lo).tolist()
+        rows = first_fit(self.tlen_cpu - 1, order, T)
+        x = torch.full((len(rows), T), self.pad_token, dtype=torch.int64)
+        y = torch.full((len(rows), T), self.ignore_index, dtype=torch.int64)
+        seg = torch.empty((len(rows), T), dtype=torch.int32)
+        for r, members in enumerate(rows):
+            at = 0
+            for m in members:
+                pl, tl = int(self.plen_cpu[m]), int(self.tlen_cpu[m])
+                row = self.table_cpu[m]
+                x[r, at:at + tl - 1] = row[:tl - 1]
+                y[r, at + pl - 1:at + tl - 1] = row[pl:tl]     # targets inside the completion only
+                seg[r, at:at + tl - 1] = at
+                at += tl - 1
+            seg[r, at:] = at                                    # the padding tail: a segment of its own
+        return x, y, seg, rows
+
+    def repack(self):
+        """Reshuffle each split's pairs (on ``generator``) and pack them again."""
+        N = len(self.table_cpu)
+        self.tables_cpu, self.rows = {}, {}
+        for split, lo, n in (("train", 0, self.n), ("val", self.n, N - self.n)):
+            if n > 0:
+                *self.tables_cpu[split], self.rows[split] = self._build(lo, n)
+        used = sum(sum(int(self.tlen_cpu[m]) - 1 for m in members) for rows in self.rows.values() for members in rows)
+        total = sum(len(rows) for rows in self.rows.values()) * self.T
+        self.fill = used / total if total else 0.0   # share of non-pad positions of the packed tables
+        if self.device is not None:
+            self.to(self.device)
+        return self
+
+    def to(self, device):
+        self.device = torch.device(device)
+        self._dev = {s: tuple(t.to(self.device) for t in tabs) for s, tabs in self.tables_cpu.items()}
+        return self
+
+    _staging = BatchSampler._staging
+
+    def draw_ix(self, split):
+        """Global draw of B*W packed-row indices of ``split`` on the CPU generator (rank-sliced)."""
+        if split not in self.tables_cpu:
+            raise ValueError(f"PackedPairSampler: the {split} split is empty ({len(self.table_cpu)} pairs, 90/10 "
+                             "split)")
+        n = len(self.rows[split])
+        ix = torch.randint(n, (self.B * self.W,), generator=self.generator)
+        return ix[self.rank * self.B:(self.rank + 1) * self.B]
+
+    def get_batch(self, split, out=None):
+        ix = self.draw_ix(split)
+        if self.device is None:
+            self.to("cuda")
+        dev = self.device
+        i, buf = self._staging(dev)
+        buf.copy_(ix)
+        ix_dev = buf.to(dev, non_blocking=True)
+        if dev.type == "cuda":
+            ev = torch.cuda.Event()
+            ev.record()
+            self._ring[i] = (buf, ev)
+        if out is None:
+            x = torch.empty((self.B, self.T), dtype=torch.int64, device=dev)
+            y = torch.empty((self.B, self.T), dtype=torch.int64, device=dev)
+            seg = torch.empty((self.B, self.T), dtype=torch.int32, device=dev)
+        else:
+            x, y, seg = out
+        xt, yt, st = self._dev[split]
+        # not on the hot path: three row gathers (the tables hold whole packed rows)
+        torch.index_select(xt, 0, ix_dev, out=x)
+        torch.index_select(yt, 0, ix_dev, out=y)
+        torch.index_select(st, 0, ix_dev, out=seg)
+        return x, y, seg

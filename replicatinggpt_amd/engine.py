@@ -20,7 +20,9 @@ A sampler with an ``ignore_index`` attribute (data.PairSampler) trains on masked
 is the mean over the batch's valid tokens, with the normaliser computed and read on the device, so
 a replayed graph follows each batch's count.  Data parallel training keeps torch-DDP semantics:
 each rank's loss is the mean over its OWN valid tokens and the gradients are averaged across ranks
-(not weighted by the ranks' token counts).
+(not weighted by the ranks' token counts).  A sampler with ``packed`` set (data.PackedPairSampler)
+also fills a third static buffer, seg_start, which the model reads on the device: one captured graph
+replays batches with different segmentations.
 
 A learning-rate schedule (``lr_schedule``: iteration -> lr) needs an optimizer in dynamic mode
 (optim.AdamW(dynamic_lr=True) or max_grad_norm): its update reads the learning rate from the device
@@ -108,6 +110,11 @@ class TrainStep:
         B, T = sampler.B, sampler.T
         self.x = torch.empty((B, T), dtype=torch.int64, device=dev)
         self.y = torch.empty((B, T), dtype=torch.int64, device=dev)
+        self._bufs = (self.x, self.y)
+        if getattr(sampler, "packed", False):   # data.PackedPairSampler: several pairs per row
+            self.seg = torch.empty((B, T), dtype=torch.int32, device=dev)
+            self._bufs += (self.seg,)
+            self._loss_kw["seg_start"] = self.seg
         self.use_graph = use_graph and dev.type == "cuda"
         self.g_fb = self.g_opt = None
         self.g_seg = []
@@ -246,7 +253,7 @@ class TrainStep:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(warmup):
-                self.sampler.get_batch("train", out=(self.x, self.y))
+                self.sampler.get_batch("train", out=self._bufs)
                 if self.overlap:
                     self._eager_segmented()
                 else:
@@ -291,7 +298,7 @@ class TrainStep:
 
     # -- one training step ----------------------------------------------------------------
     def step(self):
-        self.sampler.get_batch("train", out=(self.x, self.y))   # GPT1.py:227
+        self.sampler.get_batch("train", out=self._bufs)   # GPT1.py:227
         if self.lr_schedule is not None:
             self.opt.set_lr(self.lr_schedule(self.it))
         self.it += 1
@@ -324,20 +331,26 @@ class Evaluator:
         dev = model.flat.master.device
         self.x = torch.empty((sampler.B, sampler.T), dtype=torch.int64, device=dev)
         self.y = torch.empty_like(self.x)
+        self._bufs, self._kw = (self.x, self.y), {}
+        if getattr(sampler, "ignore_index", None) is not None:   # data.PairSampler: masked targets
+            self._kw["ignore_index"] = sampler.ignore_index
+        if getattr(sampler, "packed", False):                    # data.PackedPairSampler: packed rows
+            self.seg = torch.empty((sampler.B, sampler.T), dtype=torch.int32, device=dev)
+            self._bufs += (self.seg,)
+            self._kw["seg_start"] = self.seg
         self.use_graph = use_graph and dev.type == "cuda"
         self.graph = None
         self.out = None
 
     def _forward(self):
-        ignore = getattr(self.sampler, "ignore_index", None)   # data.PairSampler: masked targets
-        _, loss = self.model(self.x, self.y, **({} if ignore is None else {"ignore_index": ignore}))
+        _, loss = self.model(self.x, self.y, **self._kw)
         return loss
 
     @torch.no_grad()
     def loss(self, split):
         """Draw a batch of ``split`` (one get_batch, as GPT1.py:92) and return its mean loss as a
         device scalar (valid until the next call)."""
-        self.sampler.get_batch(split, out=(self.x, self.y))
+        self.sampler.get_batch(split, out=self._bufs)
         if not self.use_graph:
             return self._forward()
         if self.graph is None:

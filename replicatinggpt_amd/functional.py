@@ -649,11 +649,12 @@ def layernorm_bwd(dy2, x2, w_reg, b_reg, mean, rstd, dres=None, want_lp=False, l
     return dx, (lp if want_lp and not use_link else None), fw() + fb()
 
 
-def attention_fwd(qkv, B, T, H, D, out, scale, p, seed, rng_call, site, premask=None):
+def attention_fwd(qkv, B, T, H, D, out, scale, p, seed, rng_call, site, premask=None, seg=None):
     """Returns (lse, mask): mask holds the dropout keep bits of the MFMA path (None when p == 0
     or when the generic kernels, which regenerate Philox in place, are used).  ``premask`` =
     (mask, event): keep bits already generated -- on the side stream (the main stream waits on the
-    event instead of generating them) or, event None, earlier on this stream (layernorm_attn_mask)."""
+    event instead of generating them) or, event None, earlier on this stream (layernorm_attn_mask).
+    ``seg`` = (seg_start, seg_end) of packed rows (ops.seg_bounds): the segment-masked kernels."""
     d = H * D
     lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
     mask, ready = None, False
@@ -665,6 +666,10 @@ def attention_fwd(qkv, B, T, H, D, out, scale, p, seed, rng_call, site, premask=
     elif p > 0 and T % 16 == 0:
         mask = torch.empty(ops.attn_mask_bytes(B, H, T) // 8, dtype=torch.int64, device=qkv.device)
     if "skip_attn" in WHATIF:
+        return lse, mask
+    if seg is not None:
+        ops.attn_fwd_seg(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), out, out.stride(0), lse, float(scale), float(p),
+                         int(seed), rng_call, int(site), mask, seg[0], seg[1], ready)
         return lse, mask
     ops.attn_fwd(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), out, out.stride(0), lse, float(scale), float(p),
                  int(seed), rng_call, int(site), mask, ready)
@@ -697,11 +702,16 @@ def rowdot_ok(dy2, w, o, T, D):
     return M % T == 0 and ops.gemm_rowdot_supported(M, N, K, dy2.stride(0), w.stride(0), N)
 
 
-def attention_bwd(qkv, B, T, H, D, o, do, lse, scale, p, seed, rng_call, site, mask=None, delta=None):
+def attention_bwd(qkv, B, T, H, D, o, do, lse, scale, p, seed, rng_call, site, mask=None, delta=None, seg=None):
     d = H * D
     dqkv = torch.empty_like(qkv)
     ws = torch.empty(ops.attn_bwd_workspace(B, T, H, D) // 4, dtype=torch.float32, device=qkv.device)
     if "skip_attn" in WHATIF:
+        return dqkv
+    if seg is not None:
+        ops.attn_bwd_seg(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), o, o.stride(0), do, do.stride(0), lse, dqkv,
+                         dqkv.stride(0), float(scale), float(p), int(seed), rng_call, int(site), mask, ws, seg[0],
+                         seg[1], delta)
         return dqkv
     ops.attn_bwd(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), o, o.stride(0), do, do.stride(0), lse, dqkv,
                  dqkv.stride(0), float(scale), float(p), int(seed), rng_call, int(site), mask, ws, delta)
@@ -726,29 +736,39 @@ def _regions_params(regs):
 
 class LayerCtx:
     """Per-call context for a sublayer: geometry, dropout and dtype."""
-    __slots__ = ("n_head", "head_size", "scale", "p", "seed", "rng_call", "site", "act", "premask", "next_ln")
+    __slots__ = ("n_head", "head_size", "scale", "p", "seed", "rng_call", "site", "act", "premask", "next_ln", "seg")
 
-    def __init__(self, n_head, head_size, scale, p, seed, rng_call, site, act, premask=None, next_ln=None):
+    def __init__(self, n_head, head_size, scale, p, seed, rng_call, site, act, premask=None, next_ln=None, seg=None):
         self.n_head, self.head_size, self.scale, self.p = n_head, head_size, scale, p
         self.seed, self.rng_call, self.site, self.act = seed, rng_call, site, act
         self.premask = premask   # (mask tensor, event) from BigramLanguageModel._launch_premasks
         self.next_ln = next_ln   # (weight Region, bias Region, eps) of the LayerNorm that reads the output
+        self.seg = seg           # packed rows: (seg_start, seg_end) int32 [B, T] of this forward, else None
 
 
 # ---------------------------------------------------------------------------------------
 # fused training nodes
 # ---------------------------------------------------------------------------------------
 class EmbeddingFn(torch.autograd.Function):
-    """x = wte[idx] + wpe[arange(T)]  (GPT1.py:179-181)"""
+    """x = wte[idx] + wpe[arange(T)]  (GPT1.py:179-181); packed rows (``seg`` = (seg_start, seg_end)):
+    x = wte[idx] + wpe[t - seg_start[b, t]], the positions restarting at each segment."""
 
     @staticmethod
     def forward(ctx, idx, wte_reg, wpe_reg, *params):
+        return EmbeddingFn._forward(ctx, idx, wte_reg, wpe_reg, None)
+
+    @staticmethod
+    def _forward(ctx, idx, wte_reg, wpe_reg, seg):
         B, T = idx.shape
         V, C = wte_reg.master.shape
         x = torch.empty((B, T, C), dtype=torch.float32, device=idx.device)
-        ops.embed_fwd(idx, wte_reg.master, wpe_reg.master, x)
+        if seg is not None:
+            ops.embed_fwd_seg(idx, seg[0], wte_reg.master, wpe_reg.master, x)
+        else:
+            ops.embed_fwd(idx, wte_reg.master, wpe_reg.master, x)
         ctx.save_for_backward(idx)
         ctx.regs = (wte_reg, wpe_reg)
+        ctx.seg = seg
         return x
 
     @staticmethod
@@ -761,7 +781,15 @@ class EmbeddingFn(torch.autograd.Function):
         gp, bp, fp = wpe_reg.grad_target()
         if gt is not None or gp is not None:
             ws = torch.empty(ops.embed_bwd_workspace(B, T, C, V) // 4, dtype=torch.float32, device=dx.device)
-            if bt != bp and gt is not None and gp is not None:
+            if ctx.seg is not None:
+                se = ctx.seg[1]
+                if bt != bp and gt is not None and gp is not None:
+                    ops.embed_bwd_seg(idx, se, dx.contiguous(), gt, None, bool(bt), ws)
+                    ops.embed_bwd_seg(idx, se, dx.contiguous(), None, gp[:T], bool(bp), ws)
+                else:
+                    ops.embed_bwd_seg(idx, se, dx.contiguous(), gt, gp[:T] if gp is not None else None,
+                                      bool(bt or bp), ws)
+            elif bt != bp and gt is not None and gp is not None:
                 ops.embed_bwd(idx, dx.contiguous(), gt, None, bool(bt), ws)
                 ops.embed_bwd(idx, dx.contiguous(), None, gp[:T], bool(bp), ws)
             else:
@@ -769,7 +797,15 @@ class EmbeddingFn(torch.autograd.Function):
             if gp is not None and not bp and T < gp.shape[0]:
                 gp[T:].zero_()  # positions beyond T get no gradient (overwrite mode)
         SIDE.join(dx.device)   # last node of the model backward: every gradient is final after this
-        return (None, None, None, *ft(), *fp())
+        return (None, None, None, *((None,) if ctx.seg is not None else ()), *ft(), *fp())
+
+
+class EmbeddingSegFn(EmbeddingFn):
+    """EmbeddingFn on packed rows: ``seg`` = (seg_start, seg_end), int32 [B, T] (ops.seg_bounds)."""
+
+    @staticmethod
+    def forward(ctx, idx, seg, wte_reg, wpe_reg, *params):
+        return EmbeddingFn._forward(ctx, idx, wte_reg, wpe_reg, seg)
 
 
 class AttnSublayerFn(torch.autograd.Function):
@@ -794,7 +830,7 @@ class AttnSublayerFn(torch.autograd.Function):
         linear_fwd(a, qkv_w.operand(act), qkv)
         o = torch.empty((B * T, C), dtype=act, device=x.device)
         lse, ctx.mask = attention_fwd(qkv, B, T, lc.n_head, lc.head_size, o, lc.scale, lc.p, lc.seed, lc.rng_call,
-                                      lc.site, pm)
+                                      lc.site, pm, lc.seg)
         out = torch.empty((B * T, C), dtype=torch.float32, device=x.device)
         ln_next = linear_fwd_resid_ln(o, proj_w.operand(act), out, proj_b.master, x2, lc.next_ln, act)
         ctx.save_for_backward(x2, a, mean, rstd, qkv, o, lse)
@@ -845,7 +881,7 @@ class AttnSublayerFn(torch.autograd.Function):
         if not group:
             EARLY.region_done(proj_w, g_pw, beta_pw)   # the projection weight's last read this step
         dqkv = attention_bwd(qkv, B, T, lc.n_head, lc.head_size, o, do, lse, lc.scale, lc.p, lc.seed, lc.rng_call,
-                             lc.site, ctx.mask, delta)
+                             lc.site, ctx.mask, delta, lc.seg)
         if g is not None:
             # the pair goes out before the QKV dgrad, whose launch then hosts both reduces on its free slots
             # (after it the reduces had no host before the AdamW queue needed them: 2.8417 vs 2.7690 ms/step)
@@ -1231,7 +1267,7 @@ class MHAFn(torch.autograd.Function):
         linear_fwd(x2, qkv_w.operand(act), qkv)
         o = torch.empty((B * T, d), dtype=act, device=x.device)
         lse, ctx.mask = attention_fwd(qkv, B, T, lc.n_head, lc.head_size, o, lc.scale, lc.p, lc.seed, lc.rng_call,
-                                      lc.site, lc.premask)
+                                      lc.site, lc.premask, lc.seg)
         if proj_w is not None:
             out = torch.empty((B * T, proj_w.master.shape[0]), dtype=torch.float32, device=x.device)
             linear_fwd(o, proj_w.operand(act), out, "bias", bias=proj_b.master)
@@ -1264,7 +1300,7 @@ class MHAFn(torch.autograd.Function):
         else:
             do = to_act(d32, act)
         dqkv = attention_bwd(qkv, B, T, lc.n_head, lc.head_size, o, do, lse, lc.scale, lc.p, lc.seed, lc.rng_call,
-                             lc.site, ctx.mask)
+                             lc.site, ctx.mask, None, lc.seg)
         g, beta, f_qkv = qkv_w.grad_target()
         if g is not None:
             linear_wgrad(dqkv, x2, g, beta, g is qkv_w.slot)

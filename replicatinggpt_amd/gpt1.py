@@ -25,6 +25,8 @@ Deliberate differences from GPT1.py:
   ...}`` tokenised with the ``--input`` vocabulary -- with the loss on the completions only
   (data.PairSampler, the masked cross entropy of DESIGN.md §4); ``--init-from model.pth`` loads a state
   dict first, since fine-tuning starts from a trained model.  Without them nothing changes;
+  ``--pack`` (with ``--pairs`` only) puts several pairs in each row (data.PackedPairSampler: attention
+  masked between them, positions restarting at each) and prints the share of non-pad positions once;
 * dropout masks come from charpt's Philox stream, so with Dropout > 0 the loss
   curve matches the reference's within tolerance, not bit for bit (tests/test_gpu_train.py).
 """
@@ -35,7 +37,7 @@ import torch
 
 from . import checkpoint
 from .config import PRESETS
-from .data import DEFAULT_INPUT, BatchSampler, PairSampler, TokenStream
+from .data import DEFAULT_INPUT, BatchSampler, PackedPairSampler, PairSampler, TokenStream
 from .engine import Evaluator, TrainStep
 from .model import BigramLanguageModel
 from .optim import AdamW
@@ -55,9 +57,12 @@ def estimate_loss(model, sampler, eval_iters, evaluator=None):
             if evaluator is not None:
                 losses[k] = evaluator.loss(split)                             # :92-93, graph replay
             else:
-                X, Y = sampler.get_batch(split)                               # :92
+                X, Y, *seg = sampler.get_batch(split)                         # :92
                 ignore = getattr(sampler, "ignore_index", None)               # PairSampler: masked targets
-                _, loss = model(X, Y) if ignore is None else model(X, Y, ignore_index=ignore)   # :93
+                kw = {} if ignore is None else {"ignore_index": ignore}
+                if seg:                                                       # PackedPairSampler: packed rows
+                    kw["seg_start"] = seg[0]
+                _, loss = model(X, Y, **kw)                                   # :93
                 losses[k] = loss                                              # :94 (no host sync)
         out[split] = losses.cpu().mean()                                      # :95
     model.train()                                                             # :96
@@ -107,6 +112,8 @@ def parse_args(argv=None):
     ap.add_argument("--resume", default=None, help="continue from a --save-checkpoint file")
     ap.add_argument("--pairs", default=None, help="fine-tune on JSON lines {\"prompt\", \"completion\"}: loss on the "
                     "completions only")
+    ap.add_argument("--pack", action="store_true", help="with --pairs: several pairs per row, attention masked "
+                    "between them")
     ap.add_argument("--init-from", default=None, help="load this state dict (a --out file) before training")
     ap.add_argument("--no-graph", action="store_true", help="eager steps instead of hipGraph replay")
     return ap.parse_args(argv)
@@ -114,6 +121,8 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
+    if a.pack and not a.pairs:
+        raise SystemExit("charpt: --pack packs (prompt, completion) pairs: it needs --pairs FILE")
     print(torch.cuda.is_available())                                          # GPT1.py:7
     if not torch.cuda.is_available():
         raise SystemExit("charpt: the GPT1 driver needs an AMD GPU (HIP); the hot path has no CPU version")
@@ -141,7 +150,11 @@ def main(argv=None):
         optimizer = AdamW(m.parameters(), lr=lr)                              # GPT1.py:218
     else:
         optimizer = AdamW(m.parameters(), lr=lr, max_grad_norm=a.grad_clip, dynamic_lr=True)
-    if a.pairs:
+    if a.pairs and a.pack:
+        sampler = PackedPairSampler(read_pairs(a.pairs, tok), cfg.block_size, cfg.batch_size, device=device)
+        print(f"packed rows: {100 * sampler.fill:.1f}% of the positions hold pair tokens "
+              f"({sum(len(r) for r in sampler.rows.values())} rows)")
+    elif a.pairs:
         sampler = PairSampler(read_pairs(a.pairs, tok), cfg.block_size, cfg.batch_size, device=device)
     else:
         sampler = BatchSampler(stream, cfg.block_size, cfg.batch_size)       # GPT1.py:75-83

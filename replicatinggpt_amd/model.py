@@ -125,8 +125,9 @@ class MultiHeadAttention(nn.Module):
         rng = _snapshot_for(self, x) if p > 0 else None
         root = getattr(self, "_charpt_root", None)
         pm = root._premasks.get(self.site) if (p > 0 and root is not None and root._premasks) else None
+        seg = root._fwd_seg if root is not None else None   # packed rows: this forward's (seg_start, seg_end)
         return Fn.LayerCtx(len(self.heads), self.heads[0].key.out_features, Fn.attention_scale(C), p,
-                           self.config.dropout_seed, rng, self.site, _act_dtype(self.config), pm)
+                           self.config.dropout_seed, rng, self.site, _act_dtype(self.config), pm, seg=seg)
 
     def forward(self, x):
         _require_hip(x)
@@ -198,7 +199,9 @@ class Block(nn.Module):
         pw, pb = self.sa_heads.proj_regions()
         ln2w, ln2b = self.ln2._regions()
         lc.next_ln = (ln2w, ln2b, self.ln2.eps)   # the projection GEMM also computes ln2 (functional.pre_ln)
-        y = Fn.attn_sublayer_infer(x, lc, ln1w, ln1b, qkv, pw, pb) if not torch.is_grad_enabled() else None
+        # (a packed-row forward runs the training kernels under no_grad too: the fast paths take no mask)
+        infer = not torch.is_grad_enabled() and lc.seg is None
+        y = Fn.attn_sublayer_infer(x, lc, ln1w, ln1b, qkv, pw, pb) if infer else None
         if y is not None:   # inference: the row-resident fp32 Linears where they apply
             x = y
         else:
@@ -212,7 +215,7 @@ class Block(nn.Module):
         if nxt is not None and (att is None or not (self.training and att.heads[0].dropout.p > 0)):
             lc2.next_ln = (*nxt._regions(), nxt.eps)
         w1, b1, w2, b2 = self.ffwd.regions()
-        if not torch.is_grad_enabled():   # inference: the fused fp32 FFN where it applies
+        if infer:   # inference: the fused fp32 FFN where it applies
             y = Fn.ffn_sublayer_infer(x, lc2, ln2w, ln2b, w1, b1, w2, b2)
             if y is not None:
                 return y
@@ -371,6 +374,7 @@ class BigramLanguageModel(nn.Module):
             object.__setattr__(blk, "_charpt_next_ln", nxt)
         self._fwd_rng = None
         self._premasks = None
+        self._fwd_seg = None
         self.register_buffer("_rng_counter", torch.zeros(1, dtype=torch.int64), persistent=False)
         self._store = None
         self._pack()
@@ -454,11 +458,18 @@ class BigramLanguageModel(nn.Module):
             st.refresh_shadow()
 
     # -- forward (GPT1.py:176-194) -----------------------------------------------------
-    def forward(self, idx, targets=None, ignore_index=None):
+    def forward(self, idx, targets=None, ignore_index=None, seg_start=None):
         """``ignore_index`` (F.cross_entropy's; data.PairSampler uses -100): targets equal to it are
         left out of the loss and its gradients, the mean is over the others.  It is a launch argument
         of the masked loss kernels -- the targets are never inspected on the host.  None (default): the
-        unmasked loss of GPT1.py:192."""
+        unmasked loss of GPT1.py:192.
+
+        ``seg_start`` (int32 [B, T], data.PackedPairSampler): packed rows.  seg_start[b, t] is the index
+        of the first token of the segment (one prompt/completion pair, or the padding tail) that holds
+        position t.  Attention stays inside a segment and the positions restart at its first token, so
+        every segment is computed as if it were alone in a row of its own; the loss is still the mean
+        over the batch's valid targets.  It is read on the device only.  None (default): one sequence
+        per row."""
         _require_hip(idx)
         cfg = self.config
         idx = idx.contiguous()          # generate() passes a column slice idx[:, -block_size:]
@@ -467,6 +478,15 @@ class BigramLanguageModel(nn.Module):
         B, T = idx.shape
         if T > cfg.block_size:
             raise ValueError(f"sequence length {T} exceeds block_size {cfg.block_size}")
+        seg = None
+        if seg_start is not None:
+            if seg_start.dtype != torch.int32 or tuple(seg_start.shape) != (B, T) or seg_start.device != idx.device:
+                raise ValueError(f"seg_start must be an int32 [{B}, {T}] tensor on {idx.device} (got "
+                                 f"{seg_start.dtype} {tuple(seg_start.shape)} on {seg_start.device})")
+            seg_start = seg_start.contiguous()
+            seg_end = torch.empty_like(seg_start)
+            ops.seg_bounds(seg_start, seg_end)   # once per forward, shared by the embedding and every layer
+            seg = (seg_start, seg_end)
         act = _act_dtype(cfg)
         if act == torch.bfloat16:
             self._sync_shadow()
@@ -479,9 +499,13 @@ class BigramLanguageModel(nn.Module):
             hs = cfg.n_embd // cfg.n_head
             if Fn.SIDE.premask and Fn.premask_ok(act, T, hs) and self.blocks[0].sa_heads.heads[0].dropout.p > 0:
                 self._launch_premasks(idx.device, B, T)
+        self._fwd_seg = seg
         try:
             wte, wpe = R["wte"], R["wpe"]
-            x = Fn.EmbeddingFn.apply(idx, wte, wpe, *wte.params, *wpe.params)
+            if seg is not None:
+                x = Fn.EmbeddingSegFn.apply(idx, seg, wte, wpe, *wte.params, *wpe.params)
+            else:
+                x = Fn.EmbeddingFn.apply(idx, wte, wpe, *wte.params, *wpe.params)
             x = self.blocks(x)
             lw, lb, hw, hb = R["lnf_w"], R["lnf_b"], R["lm_w"], R["lm_b"]
             masked = () if (ignore_index is None or targets is None) else (int(ignore_index),)
@@ -490,6 +514,7 @@ class BigramLanguageModel(nn.Module):
         finally:
             self._fwd_rng = None
             self._premasks = None
+            self._fwd_seg = None
         if targets is None:
             return out, None
         return out

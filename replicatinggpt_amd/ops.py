@@ -98,6 +98,47 @@ def embed_bwd_workspace(B, T, C, V):
     return L.load().cg_embed_bwd_workspace(B, T, C, V)
 
 
+# packed rows (several pairs per row): seg_start / seg_end int32 [B, T], see cg_seg_bounds
+def _seg_check(name, B, T, ref, **segs):
+    for k, t in segs.items():
+        if t.dtype != torch.int32 or tuple(t.shape) != (B, T) or not t.is_contiguous() or t.device != ref.device:
+            raise ValueError(f"{name}: {k} must be a dense int32 [{B}, {T}] tensor on {ref.device} "
+                             f"(got {t.dtype} {tuple(t.shape)}, strides {tuple(t.stride())}, {t.device})")
+
+
+@_op("seg_bounds", ("seg_end",))
+def seg_bounds(seg_start: Tensor, seg_end: Tensor) -> None:
+    if seg_start.dim() != 2:
+        raise ValueError(f"seg_bounds: seg_start must be [B, T] (got {tuple(seg_start.shape)})")
+    B, T = seg_start.shape
+    _seg_check("seg_bounds", B, T, seg_start, seg_start=seg_start, seg_end=seg_end)
+    L.check(L.load().cg_seg_bounds(L.ptr(seg_start), L.ptr(seg_end), B, T, _s(seg_start)), "seg_bounds")
+
+
+@_op("embed_fwd_seg", ("x",))
+def embed_fwd_seg(idx: Tensor, seg_start: Tensor, wte: Tensor, wpe: Tensor, x: Tensor) -> None:
+    B, T = idx.shape
+    V, C = wte.shape
+    _seg_check("embed_fwd_seg", B, T, idx, seg_start=seg_start)
+    if wpe.shape[0] < T:
+        raise ValueError(f"embed_fwd_seg: wpe has {wpe.shape[0]} rows, T = {T}")
+    L.check(L.load().cg_embed_fwd_seg(L.ptr(idx), L.ptr(seg_start), L.ptr(wte), L.ptr(wpe), L.ptr(x), B, T, C, V,
+                                      _s(x)), "embed_fwd_seg")
+
+
+@_op("embed_bwd_seg", ("dwte", "dwpe", "ws"))
+def embed_bwd_seg(idx: Tensor, seg_end: Tensor, dx: Tensor, dwte: Optional[Tensor], dwpe: Optional[Tensor],
+                  accumulate: bool, ws: Tensor) -> None:
+    B, T = idx.shape
+    C = dx.shape[-1]
+    V = dwte.shape[0] if dwte is not None else 1
+    _seg_check("embed_bwd_seg", B, T, idx, seg_end=seg_end)
+    if dwpe is not None and dwpe.shape[0] < T:
+        raise ValueError(f"embed_bwd_seg: dwpe has {dwpe.shape[0]} rows, T = {T}")
+    L.check(L.load().cg_embed_bwd_seg(L.ptr(idx), L.ptr(seg_end), L.ptr(dx), L.ptr(dwte), L.ptr(dwpe), B, T, C, V,
+                                      int(accumulate), L.ptr(ws), _s(dx)), "embed_bwd_seg")
+
+
 # ---------------------------------------------------------------------------------------
 @_op("layernorm_fwd", ("y", "mean", "rstd"))
 def layernorm_fwd(x: Tensor, w: Tensor, b: Tensor, y: Tensor, mean: Tensor, rstd: Tensor, eps: float) -> None:
@@ -434,6 +475,37 @@ def attn_bwd(qkv: Tensor, B: int, T: int, H: int, D: int, q_off: int, k_off: int
 
 def attn_bwd_workspace(B, T, H, D):
     return L.load().cg_attn_bwd_workspace(B, T, H, D)
+
+
+@_op("attn_fwd_seg", ("o", "lse", "mask"))
+def attn_fwd_seg(qkv: Tensor, B: int, T: int, H: int, D: int, q_off: int, k_off: int, v_off: int, ld: int, o: Tensor,
+                 ld_o: int, lse: Tensor, scale: float, dropout_p: float, seed: int, rng_call: Optional[Tensor],
+                 site: int, mask: Optional[Tensor], seg_start: Tensor, seg_end: Tensor,
+                 mask_ready: bool = False) -> None:
+    """attn_fwd on packed rows: query i sees key j iff seg_start[b, i] <= j <= i (cg_attn_fwd_seg)."""
+    _seg_check("attn_fwd_seg", B, T, qkv, seg_start=seg_start, seg_end=seg_end)
+    es = qkv.element_size()
+    base = qkv.data_ptr()
+    fn = L.load().cg_attn_fwd_seg_premasked if mask_ready else L.load().cg_attn_fwd_seg
+    L.check(fn(L.dtype_code(qkv.dtype), B, T, H, D, base + q_off * es, base + k_off * es, base + v_off * es, ld,
+               L.ptr(o), ld_o, L.ptr(lse), scale, dropout_p, seed, L.ptr(rng_call), site, L.ptr(mask),
+               L.ptr(seg_start), L.ptr(seg_end), _s(qkv)), "attn_fwd_seg")
+
+
+@_op("attn_bwd_seg", ("dqkv", "ws"))
+def attn_bwd_seg(qkv: Tensor, B: int, T: int, H: int, D: int, q_off: int, k_off: int, v_off: int, ld: int, o: Tensor,
+                 ld_o: int, dout: Tensor, ld_do: int, lse: Tensor, dqkv: Tensor, ld_d: int, scale: float,
+                 dropout_p: float, seed: int, rng_call: Optional[Tensor], site: int, mask: Optional[Tensor],
+                 ws: Tensor, seg_start: Tensor, seg_end: Tensor, delta: Optional[Tensor] = None) -> None:
+    """attn_bwd on packed rows (cg_attn_bwd_seg); delta as attn_bwd's."""
+    _seg_check("attn_bwd_seg", B, T, qkv, seg_start=seg_start, seg_end=seg_end)
+    es = qkv.element_size()
+    base, dbase = qkv.data_ptr(), dqkv.data_ptr()
+    L.check(L.load().cg_attn_bwd_seg(L.dtype_code(qkv.dtype), B, T, H, D, base + q_off * es, base + k_off * es,
+                                     base + v_off * es, ld, L.ptr(o), ld_o, L.ptr(dout), ld_do, L.ptr(lse),
+                                     L.ptr(delta), dbase + q_off * es, dbase + k_off * es, dbase + v_off * es, ld_d,
+                                     scale, dropout_p, seed, L.ptr(rng_call), site, L.ptr(mask), L.ptr(seg_start),
+                                     L.ptr(seg_end), L.ptr(ws), _s(qkv)), "attn_bwd_seg")
 
 
 # ---------------------------------------------------------------------------------------
