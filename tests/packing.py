@@ -5,7 +5,10 @@
 * ``seg_of_lengths`` / ``seg_end_of`` / ``segments`` -- seg_start rows from segment lengths and back.
 * ``attn_ref_seg`` -- the dense fp64 attention reference with the block-diagonal causal mask and the
   Philox keep bits (test_gpu_ops._attn_ref plus the segment mask); ``attn_ref_alone`` -- every segment
-  run through the unmasked causal reference in a row of its own (p = 0), reassembled.
+  run through the unmasked causal reference in a row of its own (p = 0), reassembled; ``lse_ref_seg`` --
+  the masked scores' logsumexp.
+* ``RING_*`` / ``F32_*`` / ``RESCALE_*`` -- the segmentations and data recipes of the long-row op tests
+  (test_gpu_packed_attn_long.py), with ``rescale_query_tiles``: where the lazy rescale must fire.
 * ``packed_oracle`` -- the oracle run on each segment alone, reassembled: the model-level reference.
 * ``PACKED_*`` / ``packed_train_sampler`` -- the seeded short pairs of the model-level tests at shape E.
 
@@ -143,6 +146,108 @@ def attn_ref_alone(q, k, v, scale, seg_start):
             sc = sc.masked_fill(~torch.tril(torch.ones(e - s, e - s, dtype=torch.bool)), float("-inf"))
             out[b:b + 1, s:e] = torch.einsum("bhts,bshd->bthd", torch.softmax(sc, dim=-1), vs)
     return out
+
+
+def lse_ref_seg(q, k, scale, seg_start):
+    """[B, H, T] float64: logsumexp of the scaled scores under the segment mask (independent of dropout)."""
+    s = torch.einsum("bthd,bshd->bhts", q, k) * scale
+    return torch.logsumexp(s.masked_fill(~seg_mask(seg_start)[:, None], float("-inf")), dim=-1)
+
+
+# ---------------------------------------------------------------------------------------
+# long rows (test_gpu_packed_attn_long.py; held without a GPU by test_cpu_packing.py)
+# ---------------------------------------------------------------------------------------
+def cycling(T, top=40):
+    """Lengths 1, 2, .. top, 1, .. for as long as the next one fits; what is left is the last segment."""
+    out, at, n = [], 0, 1
+    while at + n <= T:
+        out.append(n)
+        at, n = at + n, n % top + 1
+    return out
+
+
+# bf16 D 64 beyond T 256: the ring kernels.  256-query blocks run as (last, x) pass pairs per workgroup
+# (T 576: blocks (2, 0) and the single pass 1; T 1024: (3, 0) and (2, 1)), the dK/dV kernel cuts keys in
+# blocks of 128.  The lists put bounds on 256 k and either side of it, on 128 k +- 1, segments that start in
+# every query block >= 1 (whole leading tiles skipped while the keep words advance), long single segments
+# that begin late ([300], [513]) and many short ones.
+RING_SHAPES = [(2, 512, 2), (2, 576, 3), (1, 1024, 2)]   # B, T, H
+RING_SEGS = {
+    512: [[], [256], [255, 2], [257, 1, 200], [128, 128, 128], [127, 2, 127, 129], [300], [10, 490], [273, 40, 7],
+          cycling(512)],
+    576: [[], [512], [511, 2], [513], [300], [64] * 8, [200, 150, 100], [320, 1, 1, 200]],
+    1024: [[], [512], [767, 2, 200], [700, 300]],
+}
+# (T, lengths, index of the kept segment): one across the query-block edge at 256, one wholly inside the last
+# query block, the first; at T 1024 one inside the last block of a two-workgroup grid
+RING_LEAK = {"straddle": (576, [200, 150, 100], 1), "last-block": (576, [200, 150, 170, 30], 3),
+             "first": (576, [200, 150, 100], 0), "last-block-1024": (1024, [300, 500, 100], 2)}
+
+# fp32, D <= 32, p = 0: the MFMA forward in 64-query blocks of 4 waves x 16 queries over 64-key tiles.
+# Bounds on 64 k and either side, on a wave's 16-query edge and either side ([79, 2, ..], [81], 16 k), inside a
+# wave ([70, ..]: tiles masked for some of its lanes only), segments that start at >= 64 and >= 128 (whole
+# tiles masked for every query of a wave), length-1 segments on a tile edge, and [].
+F32_SHAPES = [(2, 130, 4, 16), (2, 200, 2, 8), (2, 256, 2, 32), (1, 300, 3, 21)]   # B, T, H, D
+F32_SEGS = {
+    130: [[], [64], [63, 2], [65, 1, 62], [81], [70, 58, 1], [128, 1], [127, 1, 1], [129], [16, 48, 1, 63],
+          [79, 2, 31]],
+    200: [[], [79, 2, 80], [81], [64, 64, 64], [63, 2, 63, 2, 63], [128, 48], [129, 1, 60], [100, 92], [192, 1],
+          [127, 1, 64]],
+    256: [[], [64, 64, 64], [63, 2, 127, 1, 62], [65, 127], [79, 2, 80], [81, 95], [128, 127], [129, 63, 1],
+          [200, 50], [255]],
+    300: [[], [256], [255, 2], [257, 1, 41], [64, 64, 64, 64], [79, 2, 79, 130], [81, 47, 129], [192, 100],
+          [290, 9], [63, 1, 64, 1, 127, 1]],
+}
+F32_LEAK = {130: [60, 44, 10], 300: [70, 122, 64]}
+
+
+def seg_batches(rows, B, T):
+    """The segmentations ``rows`` of T as seg_start tensors [B, T], B rows at a time (the first ones again
+    to fill the last batch): different rows of a batch get different segmentations."""
+    rows = rows + rows[:(-len(rows)) % B]
+    return [torch.stack([seg_of_lengths(r, T) for r in rows[i:i + B]]) for i in range(0, len(rows), B)]
+
+
+# the lazy rescale forced inside a segment (bf16 D 64, H 2): (T, lengths)
+RESCALE_THR = 8.0          # attention_common.h: the running max moves when a tile's max exceeds it by 2^8
+RESCALE_MIN_SEGMENT = 130
+RESCALE_RECIPES = [(256, [40, 200]), (512, [100, 250]), (1024, [300, 5, 400])]
+
+
+def rescale_data(T, lengths, H=2, D=64, seed=31):
+    """test_attention_forward_rescale_branch's recipe inside every segment of >= 130 positions: queries that
+    share a direction, one key row (at 70 % of the segment) that matches it strongly, and the first head's
+    key norms growing over the segment.  Returns qkv [T, 3 H D] bf16, the seg_start row and scale."""
+    g = torch.Generator().manual_seed(seed)
+    d = H * D
+    seg_row = seg_of_lengths(lengths, T)
+    qkv = torch.randn(T, 3 * d, generator=g) * 0.5
+    qkv[:, :d] += 2.0
+    for s, e in segments(seg_row):
+        n = e - s
+        if n >= RESCALE_MIN_SEGMENT:
+            qkv[s + int(0.7 * n), d:2 * d] = 8.0
+            qkv[s:e, d:d + D] *= torch.linspace(0.1, 3.0, n)[:, None]
+    return qkv.to(torch.bfloat16), seg_row, D ** -0.5
+
+
+def rescale_fires(q, k, scale, seg_row):
+    """bool [H, T, tiles - 1]: (head, query, 64-key tile t + 1) at which the kernels' lazy rescale must fire --
+    the tile (absolute tiles, as the kernels cut them) is not the query's first visible one and its maximum
+    exceeds that of the query's earlier visible tiles by more than RESCALE_THR in log2 units.  q, k
+    [1, T, H, D] float64.  (The kernels' stale running max never exceeds the true one.)"""
+    T = q.shape[1]
+    s = torch.einsum("bthd,bshd->bhts", q, k)[0] * (scale * 1.4426950408889634)
+    s = s.masked_fill(~seg_mask(seg_row[None])[0][None], float("-inf"))
+    tm = s.view(s.shape[0], T, T // 64, 64).amax(-1)                    # [H, T, tiles]
+    before = torch.cummax(tm, dim=-1).values[..., :-1]
+    return (before > float("-inf")) & (tm[..., 1:] > before + RESCALE_THR)
+
+
+def rescale_query_tiles(q, k, scale, seg_row):
+    """{(start, end): n} per segment: how many (head, query, tile) triples of rescale_fires it holds."""
+    per_query = rescale_fires(q, k, scale, seg_row).sum((0, 2))
+    return {(a, b): int(per_query[a:b].sum()) for a, b in segments(seg_row)}
 
 
 # ---------------------------------------------------------------------------------------

@@ -163,6 +163,126 @@ def test_all_zero_seg_start_is_the_causal_reference():
     assert torch.equal(PK.attn_ref_seg(q, k, v, 0.5, seg), ref)
 
 
+# ---------------------------------------------------------------------------------------
+# the tables of the long-row op tests (packing.RING_* / F32_* / RESCALE_*, test_gpu_packed_attn's T 192)
+# ---------------------------------------------------------------------------------------
+def _t192():
+    import test_gpu_packed_attn as A   # plain tables; nothing in it touches a device at import
+    return A.SEGS[192], A.LEAK[192]
+
+
+def _tables():
+    segs192, leak192 = _t192()
+    out = [("ring", T, rows) for T, rows in PK.RING_SEGS.items()] + [("f32", T, rows) for T, rows in PK.F32_SEGS.items()]
+    return out + [("resident", 192, segs192)]
+
+
+def bounds(rows):
+    """Every position at which a segment other than the first starts, over the rows of a table."""
+    return {at for r in rows for at in torch.tensor([0] + r).cumsum(0).tolist()[1:]}
+
+
+def test_long_tables_fit_their_rows():
+    for _, T, rows in _tables():
+        assert all(sum(r) <= T and min(r, default=1) >= 1 for r in rows), (T, rows)
+    assert sum(_t192()[1]) <= 192
+    assert all(sum(l) <= T and 0 <= n < len(PK.segments(PK.seg_of_lengths(l, T))) for T, l, n in PK.RING_LEAK.values())
+    assert all(sum(l) <= T for T, l in list(PK.F32_LEAK.items()) + PK.RESCALE_RECIPES)
+    assert {T for _, T, _ in PK.RING_SHAPES} == set(PK.RING_SEGS) and {s[1] for s in PK.F32_SHAPES} == set(PK.F32_SEGS)
+    assert set(PK.F32_LEAK) <= set(PK.F32_SEGS)
+    assert sum(PK.cycling(512)) <= 512 < sum(PK.cycling(512)) + len(PK.cycling(512)) + 1 and PK.cycling(512)[:3] == [1, 2, 3]
+
+
+@pytest.mark.parametrize("kind,T,rows", [t for t in _tables() if t[1] <= 576],
+                         ids=[f"{k}-{T}" for k, T, _ in _tables() if T <= 576])
+def test_long_tables_dense_reference_is_each_segment_alone(kind, T, rows):
+    g = torch.Generator().manual_seed(3)
+    B, H, D = 2, 1, 4
+    q, k, v = (torch.randn(B, T, H, D, generator=g, dtype=torch.float64) for _ in range(3))
+    for seg in PK.seg_batches(rows, B, T):
+        a, b = PK.attn_ref_seg(q, k, v, 0.3, seg), PK.attn_ref_alone(q, k, v, 0.3, seg)
+        assert float((a - b).abs().max()) < 1e-13
+        assert torch.equal(PK.seg_end_of(seg)[0], torch.tensor(
+            [e for s, e in PK.segments(seg[0]) for _ in range(e - s)], dtype=torch.int32))
+
+
+def test_ring_tables_hold_their_edge_classes():
+    """Per T: [] is there; a bound on 256 k and on each side of one; a bound on 128 k - 1 and 128 k + 1; a
+    segment starting in every 256-query block >= 1 (T 1024: blocks 2 and 3 -- its four rows are all the fp64
+    reference affords; block 1 gets its start from RING_LEAK's T 1024 row, the bitwise test)."""
+    for T, rows in PK.RING_SEGS.items():
+        bs = bounds(rows)
+        assert [] in rows
+        assert {0, 1, 255} <= {b % 256 for b in bs}, (T, sorted(bs))
+        assert {1, 127} <= {b % 128 for b in bs}, (T, sorted(bs))
+        blocks = set(range(1, (T + 255) // 256)) - ({1} if T == 1024 else set())
+        assert blocks <= {b // 256 for b in bs}, (T, sorted(bs))
+        assert any(max(r, default=0) >= 300 for r in rows)          # a run of leading tiles skipped whole
+    T, lengths, n = PK.RING_LEAK["last-block-1024"]
+    assert 1 in {b // 256 for b in bounds([lengths])}
+    for which, (T, lengths, n) in PK.RING_LEAK.items():
+        s, e = PK.segments(PK.seg_of_lengths(lengths, T))[n]
+        last = (T - 1) // 256 * 256
+        if which == "straddle":
+            assert s < 256 < e
+        elif which.startswith("last-block"):
+            assert last <= s and e < T
+        else:
+            assert s == 0
+
+
+def test_f32_tables_hold_their_edge_classes():
+    """Per T: []; bounds on 64 k and either side; on a wave's 16-query edge away from 64 k, one either side;
+    a bound inside a wave; segments that start at >= 64 and at >= 128; a length-1 segment on a tile edge."""
+    for T, rows in PK.F32_SEGS.items():
+        bs = bounds(rows)
+        assert [] in rows
+        assert {0, 1, 63} <= {b % 64 for b in bs}, (T, sorted(bs))
+        on16 = {b % 64 for b in bs}
+        assert on16 & {15, 31, 47} and on16 & {16, 32, 48} and on16 & {17, 33, 49}, (T, sorted(bs))
+        assert any(b % 16 not in (0, 1, 15) for b in bs), (T, sorted(bs))
+        assert any(64 <= b < 128 for b in bs) and any(b >= 128 for b in bs), (T, sorted(bs))
+        ones = [s for r in rows for s, e in PK.segments(PK.seg_of_lengths(r, T)) if e - s == 1]
+        assert any(s % 64 in (0, 63) for s in ones), (T, ones)
+    for T, lengths in PK.F32_LEAK.items():
+        spans = PK.segments(PK.seg_of_lengths(lengths, T))
+        assert len(spans) >= 3 and spans[1][0] < 64 * (spans[1][1] // 64) and spans[-1][0] >= 64
+
+
+def test_resident_192_table_holds_its_edge_classes():
+    segs, leak = _t192()
+    assert [] in segs and {63, 64, 65, 128, 129} <= bounds(segs)
+    assert len(PK.segments(PK.seg_of_lengths(leak, 192))) >= 3
+
+
+@pytest.mark.parametrize("T,lengths", PK.RESCALE_RECIPES, ids=[f"T{T}" for T, _ in PK.RESCALE_RECIPES])
+def test_rescale_recipes_force_the_rescale_in_every_long_segment(T, lengths):
+    """The precondition test_forced_rescale_inside_a_segment asserts again before its device call: every
+    segment of >= 130 positions has queries with a later visible 64-key tile more than RESCALE_THR (log2
+    units) above their earlier ones; shorter segments are left alone and have none."""
+    H, D = 2, 64
+    d = H * D
+    qkv, seg_row, scale = PK.rescale_data(T, lengths, H, D)
+    q, k = (qkv[:, j * d:(j + 1) * d].double().view(1, T, H, D) for j in range(2))
+    fires = PK.rescale_query_tiles(q, k, scale, seg_row)
+    print(fires)
+    long = [sp for sp in fires if sp[1] - sp[0] >= PK.RESCALE_MIN_SEGMENT]
+    assert len(long) == {256: 1, 512: 2, 1024: 3}[T]
+    assert all(fires[sp] > 0 for sp in long), fires
+    assert all(fires[sp] == 0 for sp in fires if sp not in long), fires
+    # rescale_fires against its plain statement, for the last query of the last long segment (head 0)
+    s, e = long[-1]
+    i = e - 1
+    sc = (k[0, s:i + 1, 0] @ q[0, i, 0]) * scale * 1.4426950408889634
+    tiles = {}
+    for j in range(s, i + 1):
+        tiles[j // 64] = max(tiles.get(j // 64, float("-inf")), float(sc[j - s]))
+    order = sorted(tiles)
+    plain = [t for n, t in enumerate(order) if n and tiles[t] > max(tiles[u] for u in order[:n]) + PK.RESCALE_THR]
+    got = (torch.nonzero(PK.rescale_fires(q, k, scale, seg_row)[0, i]).flatten() + 1).tolist()
+    assert got == plain and len(plain) >= 1, (got, plain)
+
+
 def test_packed_oracle_of_one_segment_rows_is_the_oracle():
     """Rows that hold one pair and no padding: packed_oracle is O.loss_and_grads on the batch."""
     from oracle import gpt1_oracle as O

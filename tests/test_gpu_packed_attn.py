@@ -1,9 +1,9 @@
 """Segment-masked attention (cg_attn_fwd_seg / cg_attn_bwd_seg) at the op level: against the dense fp64
 reference with the block-diagonal causal mask (tests/packing.py), bitwise against the unsegmented entry
 points for an all-zero seg_start, bitwise independence of a segment from its neighbours' data, and the
-precomputed-delta form.  Shapes: the sequence-resident bf16 kernels (D 64, T 64 / 128 / 256), the
+precomputed-delta form.  Shapes: the sequence-resident bf16 kernels (D 64, T 64 / 128 / 192 / 256), the
 generic kernels (fp32 D 21 -- its forward at p = 0 the fp32 MFMA kernel --, bf16 D 32) and long bf16 rows
-(D 64, T 320: the ring kernels)."""
+(D 64, T 320: the ring kernels; longer rows, more heads: test_gpu_packed_attn_long.py)."""
 import pytest
 import torch
 
@@ -49,6 +49,7 @@ def relerr(a, b):
 SEGS = {
     64: [[], [32], [31, 2], [33, 1, 10], [16, 1, 19, 20], [63]],
     128: [[], [64], [63, 2, 1], [65, 31], [32, 64, 7], [100, 1], [77, 20, 20]],
+    192: [[], [64, 64], [63, 2, 63, 2], [65, 63, 33], [128], [129, 50], [96, 1, 95]],
     256: [[], [64, 64, 64], [63, 2, 63, 2, 100], [65, 63, 33, 31], [128], [129, 100], [140, 1, 50],
           [32, 32, 100, 37, 40]],
     37: [[], [5, 1, 20], [36], [12, 12]],
@@ -58,6 +59,8 @@ SEGS = {
 #        dtype B  T    H  D
 RESIDENT = [(BF, 2, 64, 2, 64), (BF, 2, 128, 2, 64), (BF, 2, 256, 2, 64)]
 GENERIC = [(F32, 2, 37, 3, 21), (BF, 1, 96, 1, 32), (BF, 1, 320, 1, 64)]
+RESIDENT_NT3 = [(BF, 2, 192, 2, 64)]   # resident too; listed last so that the ids of the cases above stay
+SHAPES = RESIDENT + GENERIC + RESIDENT_NT3
 
 
 def batches(B, T):
@@ -67,7 +70,7 @@ def batches(B, T):
     return [torch.stack([PK.seg_of_lengths(r, T) for r in rows[i:i + B]]) for i in range(0, len(rows), B)]
 
 
-CASES = [(dt, B, T, H, D, i) for dt, B, T, H, D in RESIDENT + GENERIC for i in range(len(batches(B, T)))]
+CASES = [(dt, B, T, H, D, i) for dt, B, T, H, D in SHAPES for i in range(len(batches(B, T)))]
 
 
 def make(dt, B, T, H, D, seed=4):
@@ -130,7 +133,7 @@ def test_against_dense_reference(dt, B, T, H, D, i, p):
 
 
 @pytest.mark.parametrize("p", [0.0, 0.2])
-@pytest.mark.parametrize("dt,B,T,H,D", RESIDENT + GENERIC)
+@pytest.mark.parametrize("dt,B,T,H,D", SHAPES)
 def test_all_zero_seg_start_is_the_unsegmented_entry_point(dt, B, T, H, D, p):
     """One segment per row: o, lse, dq, dk and dv are bitwise those of cg_attn_fwd / cg_attn_bwd.
     A segmented call runs the kernel family of the unsegmented call of its shape."""
@@ -145,20 +148,26 @@ def test_all_zero_seg_start_is_the_unsegmented_entry_point(dt, B, T, H, D, p):
 
 
 LEAK = {64: [13, 20, 1, 18], 128: [40, 30, 33, 20], 256: [70, 61, 66, 40], 37: [9, 11, 10], 96: [31, 34, 20],
-        320: [100, 97, 90]}
+        320: [100, 97, 90], 192: [50, 47, 55, 20]}
 
 
 @pytest.mark.parametrize("p", [0.0, 0.2])
 @pytest.mark.parametrize("which", ["first", "middle", "last"])
-@pytest.mark.parametrize("dt,B,T,H,D", RESIDENT + GENERIC)
+@pytest.mark.parametrize("dt,B,T,H,D", SHAPES)
 def test_no_leak_between_segments_bitwise(dt, B, T, H, D, which, p):
     """Two runs whose q / k / v / dout differ in every segment but one (other values, large finite ones
     among them): the kept segment's o, lse, dq, dk and dv are bit-identical.  A mask that is off by one
     key or one query cannot pass, nor can a running maximum shared between the segments of a wave."""
     seg_row = PK.seg_of_lengths(LEAK[T], T)
-    seg_start = seg_row[None].repeat(B, 1)
     spans = PK.segments(seg_row)
-    s, e = {"first": spans[0], "middle": spans[1], "last": spans[-1]}[which]
+    no_leak(dt, B, T, H, D, seg_row, {"first": spans[0], "middle": spans[1], "last": spans[-1]}[which], p)
+
+
+def no_leak(dt, B, T, H, D, seg_row, span, p):
+    """The statement of test_no_leak_between_segments_bitwise for the segment ``span`` of ``seg_row`` (every
+    row of the batch segmented alike)."""
+    s, e = span
+    seg_start = seg_row[None].repeat(B, 1)
     qkv, dout, scale = make(dt, B, T, H, D, seed=21)
     qkv2, dout2, _ = make(dt, B, T, H, D, seed=22)
     g = torch.Generator().manual_seed(23)
@@ -185,7 +194,7 @@ def test_no_leak_between_segments_bitwise(dt, B, T, H, D, which, p):
 
 
 @pytest.mark.parametrize("p", [0.0, 0.2])
-@pytest.mark.parametrize("T", [64, 128, 256])
+@pytest.mark.parametrize("T", [64, 128, 256, 192])
 def test_precomputed_delta_gives_the_bits_of_the_form_that_computes_it(T, p):
     """cg_attn_bwd_seg with delta = the rowsum(dO * O) its dQ half left in the workspace: dq, dk and dv
     bit for bit those of the call without it (the resident kernels then load neither O nor sum it)."""

@@ -100,7 +100,7 @@ def run(dt, B, T, H, D, p, lay, premasked=False, delta=False):
 
 
 SHAPES = [(BF16, 2, 128, 2, 64, "P"), (BF16, 1, 64, 1, 64, "P"), (F32, 2, 37, 3, 21, "O"), (BF16, 1, 96, 1, 32, "P"),
-          (BF16, 1, 320, 1, 64, "P")]
+          (BF16, 1, 320, 1, 64, "P"), (BF16, 2, 576, 2, 64, "P"), (F32, 2, 130, 4, 16, "O")]
 
 
 @pytest.mark.parametrize("p", [0.0, 0.2])

@@ -72,6 +72,40 @@ def test_fp32_logits_loss_and_gradients_match_the_packed_oracle():
         assert relmax(m(x)[0], rlog) > 1e-2
 
 
+LONG_F32_SHAPE = dict(block_size=160, n_embd=42, n_head=2, n_layers=1, B=2)
+
+
+def test_fp32_long_rows_match_the_packed_oracle():
+    """Rows of 160 tokens holding eight to twelve pairs (2 heads of 21, 1 layer): the fp32 MFMA forward
+    under a segment mask over three key tiles, segments that start beyond keys 64 and 128, and wpe
+    positions that restart beyond index 64.  Bars as test_fp32_logits_loss_and_gradients_match_the_packed_oracle."""
+    from replicatinggpt_amd import BigramLanguageModel
+    from replicatinggpt_amd.data import PackedPairSampler
+    torch.manual_seed(PK.E2E_INIT_SEED)
+    m = BigramLanguageModel(gpt_config("fp32", LONG_F32_SHAPE)).to(DEV)
+    s = PackedPairSampler(PK.PACKED_PAIRS, 160, 2, generator=torch.Generator().manual_seed(2), device=DEV)
+    x, y, seg = s.get_batch("train")
+    nseg = [len(PK.segments(r)) for r in seg.cpu()]
+    print("segments per row", nseg)
+    assert min(nseg) >= 6, nseg
+    assert all(max(a for a, _ in PK.segments(r)) >= 128 for r in seg.cpu())
+    ocfg, P = oracle_of(m)
+    rlog, rloss, rg = PK.packed_oracle(P, x.cpu(), y.cpu(), seg.cpu(), ocfg)
+    with torch.no_grad():
+        logits, none = m(x, seg_start=seg)
+    assert none is None and relmax(logits, rlog) < tj.FP32_GRAD
+    lg2, loss = m(x, y, ignore_index=s.ignore_index, seg_start=seg)
+    loss.backward()
+    torch.cuda.synchronize()
+    assert relmax(lg2.view(logits.shape), rlog) < tj.FP32_GRAD
+    assert abs(float(loss) - float(rloss)) < tj.FP32_LOSS, (float(loss), float(rloss))
+    worst = {n: relmax(p.grad, rg[n]) for n, p in m.named_parameters()}
+    print("fp32 packed, long rows: worst", max(worst.items(), key=lambda kv: kv[1]))
+    assert max(worst.values()) < tj.FP32_GRAD, worst
+    with torch.no_grad():
+        assert relmax(m(x)[0], rlog) > 1e-2
+
+
 def test_bf16_loss_and_gradients_match_the_packed_oracle():
     """Shape E (block 64, n_embd 128, 2 heads of 64: the sequence-resident kernels, 2 layers), rows of
     three to five segments."""
