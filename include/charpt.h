@@ -541,6 +541,35 @@ int cg_decode_emit(const float* logits, int64_t ldl, int64_t V, int64_t B, int m
                    const uint64_t* seed_dev, const int64_t* len_dev, const int64_t* prompt_len, const int64_t* limit,
                    int64_t* end, const uint64_t* stop_bits, const int64_t* pad_dev, int64_t* idx, int64_t ld,
                    float* logprob, void* stream);
+/* One-pass prompt prefill: the attention of P per-token steps in one launch, and the K/V cache they
+   leave.  q, k, v: the fp32 rows of a layer's QKV product for B x P positions, row b*P + t, element
+   h*D + e of each (three base pointers; row stride stride_q for q, stride_kv for both k and v).
+     kcache / vcache [B, H, Tmax, D] (dense): rows t < P of every (b, h) <- the k / v rows, exact
+       copies; rows t >= P are not written.
+     o (row b*P + t, element h*D + e, row stride stride_o): bit for bit what cg_decode_attn returns
+       for that (b, h) with q's row b*P + t as the query and nkeys = t + 1 keys of that cache.
+   The per-query arithmetic is cg_decode_attn's, one wave per position: keys in chunks of 64, key
+   64c + lane on lane `lane`; the score an fmaf chain over e < DP (D padded to 24 or 64 with zeros),
+   times scale; online softmax statistics per chunk (wave max, __expf, wave sum); acc[e] =
+   fmaf(p, v[e], acc[e] * alpha); one wave sum per dimension and * (1 / l) at the end -- the kernels
+   share that code, so a prefill by this call and a prefill by P decode steps leave the same bits.
+   q == NULL and o == NULL: the cache rows only (a last layer whose outputs nobody reads).  Reads
+   nothing outside the P rows' H*D elements, writes nothing but the cache rows and o elements named
+   above.  D <= 64, 1 <= P <= Tmax, every stride >= H*D, every pointer 4-B aligned, q and o both
+   NULL or both given, else CG_EINVAL.                                                              */
+int cg_decode_prefill_attn(const float* q, int64_t stride_q, const float* k, const float* v, int64_t stride_kv,
+                           int64_t B, int64_t P, int64_t H, int64_t D, int64_t Tmax, float scale, float* kcache,
+                           float* vcache, float* o, int64_t stride_o, void* stream);
+/* The log-probabilities of a one-pass prefill: for logits row b*P + t (fp32, V columns, row stride
+   stride_logits; the model's output at position t of row b), logprob[b, t + 1] <- log
+   softmax(row)[idx[b, t + 1]], t < P, computed by the code of cg_decode_emit's step 4 -- the same
+   bits, NaN for a row holding NaN or +inf and for a token outside [0, V) (nothing is read there)
+   included.  idx [B, > P] int64 (row stride stride_idx) is only read; of logprob (row stride
+   stride_logprob) only columns 1..P are written.  V >= 1, stride_logits >= V, both other strides
+   > P, else CG_EINVAL.                                                                             */
+int cg_decode_logprob_rows(const float* logits, int64_t stride_logits, int64_t V, int64_t B, int64_t P,
+                           const int64_t* idx, int64_t stride_idx, float* logprob, int64_t stride_logprob,
+                           void* stream);
 
 /* ---- fused AdamW over a flat fp32 buffer (torch.optim.AdamW, GPT1.py:218,233) ------------
    step_ptr: device int64 step count (already incremented for this step).

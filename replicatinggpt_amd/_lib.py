@@ -127,6 +127,9 @@ _SIGS = {
     "cg_decode_sample": (c_int, [P, c_i64, c_i64, c_i64, c_int, P, P, P, c_i64, P]),
     "cg_decode_sample_filtered": (c_int, [P, c_i64, c_i64, c_i64, P, P, P, P, c_i64, P]),
     "cg_decode_emit": (c_int, [P, c_i64, c_i64, c_i64, c_int, P, P, P, P, P, P, P, P, P, c_i64, P, P]),
+    "cg_decode_prefill_attn": (c_int, [P, c_i64, P, P, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_flt, P, P, P, c_i64,
+                                       P]),
+    "cg_decode_logprob_rows": (c_int, [P, c_i64, c_i64, c_i64, c_i64, P, c_i64, P, c_i64, P]),
     "cg_adamw": (c_int, [P, P, P, P, P, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, P, P]),
     "cg_adamw_defer": (c_int, [P, P, P, P, P, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, P, P]),
     "cg_adamw_segments": (c_int, [P, P, P, P, P, P, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, P, P]),

@@ -11,7 +11,9 @@
 // stream; cg_decode_sample_filtered: that draw under a temperature, a top-k and a top-p cut read
 // from device memory; cg_decode_emit: either, as the per-row epilogue of a ragged batch -- forced
 // prompt tokens, stop tokens, per-row limits, log-probabilities).  Every step's shapes are static and the current length lives in device
-// memory, so each phase is captured once as a hipGraph and replayed per token.
+// memory, so each phase is captured once as a hipGraph and replayed per token.  A prompt's shared positions
+// are prefilled in one pass (cg_decode_prefill_attn: phase 1's attention for every position at once, the
+// same arithmetic per position; cg_decode_logprob_rows: cg_decode_emit's log-prob for every scored column).
 #include "common.h"
 
 namespace cg {
@@ -56,6 +58,49 @@ __global__ void k_decode_kv_append(const float* __restrict__ qkv, int64_t ld, in
     vc[dst] = qkv[b * ld + v_off + h * D + e];
 }
 
+// The per-query value chain of cg_decode_attn, shared by every kernel that must give its bits
+// (k_decode_attn, k_decode_attn_rows, k_decode_prefill_attn).  One wave per query; a chunk is 64 keys,
+// key 64 c + lane on lane `lane`, kv / vv that key's row padded with zeros to DP (ok: the key is one
+// of the query's n).  attn_chunk: s as the fmaf chain over e < DP, s * scale, the online statistics
+// (wave_max / __expf / wave_sum) and acc[e] = fmaf(p, v, acc[e] * alpha).  attn_finish: the output
+// row, element e on lane e (a wave_sum_dpp per dimension, * (1 / l)).
+template <int DP>
+__device__ __forceinline__ void attn_chunk(const float (&qv)[DP], const float (&kv)[DP], const float (&vv)[DP], bool ok,
+                                           float scale, float& m, float& l, float (&acc)[DP]) {
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < DP; ++e) s = fmaf(qv[e], kv[e], s);
+    s = ok ? s * scale : -INFINITY;
+    const float m_new = fmaxf(m, wave_max(s));
+    const float alpha = __expf(m - m_new);
+    const float p = ok ? __expf(s - m_new) : 0.f;
+    l = l * alpha + wave_sum(p);
+    m = m_new;
+#pragma unroll
+    for (int e = 0; e < DP; ++e) acc[e] = fmaf(p, vv[e], acc[e] * alpha);
+}
+
+template <int DP>
+__device__ __forceinline__ float attn_finish(const float (&acc)[DP], float l, int64_t D, int lane) {
+    const float inv = 1.f / l;
+    float out = 0.f;
+#pragma unroll
+    for (int e = 0; e < DP; ++e) {
+        if (e < D) {   // wave-uniform
+            const float t = wave_sum_dpp(acc[e]);
+            out = lane == e ? t * inv : out;
+        }
+    }
+    return out;
+}
+
+// XCD-contiguous work order: block id runs on XCD id % 8, so work item xcd_contiguous(id, nblk) gives
+// every XCD one contiguous run of the nblk items (the first nblk % 8 XCDs one item more).
+__device__ __forceinline__ int64_t xcd_contiguous(int id, int nblk) {
+    const int nq = nblk >> 3, nr = nblk & 7, xcd = id & 7;
+    return (xcd < nr ? xcd * (nq + 1) : nr * (nq + 1) + (xcd - nr) * nq) + (id >> 3);
+}
+
 // one wave per (b, h): the newest query against cached keys 0..n-1 (causal by construction),
 // scale = n_embd^-0.5.  Keys are spread over the lanes -- chunk c holds key 64 c + lane
 // -- and each lane keeps its key's whole dot product and its own partial output row acc[0..D) (D
@@ -97,27 +142,9 @@ __global__ __launch_bounds__(256) void k_decode_attn(const float* __restrict__ q
             kv[e] = e < D ? kr[e] : 0.f;
             vv[e] = e < D ? vr[e] : 0.f;
         }
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < DP; ++e) s = fmaf(qv[e], kv[e], s);
-        s = ok ? s * scale : -INFINITY;
-        const float m_new = fmaxf(m, wave_max(s));
-        const float alpha = __expf(m - m_new);
-        const float p = ok ? __expf(s - m_new) : 0.f;
-        l = l * alpha + wave_sum(p);
-        m = m_new;
-#pragma unroll
-        for (int e = 0; e < DP; ++e) acc[e] = fmaf(p, vv[e], acc[e] * alpha);
+        attn_chunk<DP>(qv, kv, vv, ok, scale, m, l, acc);
     }
-    const float inv = 1.f / l;
-    float out = 0.f;
-#pragma unroll
-    for (int e = 0; e < DP; ++e) {
-        if (e < D) {   // wave-uniform
-            const float t = wave_sum_dpp(acc[e]);
-            out = lane == e ? t * inv : out;
-        }
-    }
+    const float out = attn_finish<DP>(acc, l, D, lane);
     if (lane < D) o[b * ldo + h * D + lane] = out;
 }
 
@@ -148,8 +175,7 @@ __global__ __launch_bounds__(64) void k_decode_attn_rows(const float* __restrict
     const int lane = threadIdx.x;
     // XCD-contiguous (b, h) (block i runs on XCD i % 8): a sequence's heads share one L2 -- with the
     // window's row-strided K / V (SJ) each head reads 84 B of every 1 KB row
-    const int nblk = (int)gridDim.x, id = (int)blockIdx.x, nq = nblk >> 3, nr = nblk & 7, xcd = id & 7;
-    const int64_t bh = (xcd < nr ? xcd * (nq + 1) : nr * (nq + 1) + (xcd - nr) * nq) + (id >> 3);
+    const int64_t bh = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
     const int64_t b = bh / H, h = bh % H;
     const int64_t n = len_dev ? *len_dev : nfix;  // keys 0..n-1
     const float4* K4 = (const float4*)(kc + b * sb + h * sh);
@@ -243,28 +269,98 @@ __global__ __launch_bounds__(64) void k_decode_attn_rows(const float* __restrict
             kv[e] = e < D ? ks[lane * D + e] : 0.f;
             vv[e] = e < D ? vs[lane * D + e] : 0.f;
         }
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < DP; ++e) s = fmaf(qv[e], kv[e], s);
-        s = ok ? s * scale : -INFINITY;
-        const float m_new = fmaxf(m, wave_max(s));
-        const float alpha = __expf(m - m_new);
-        const float p = ok ? __expf(s - m_new) : 0.f;
-        l = l * alpha + wave_sum(p);
-        m = m_new;
-#pragma unroll
-        for (int e = 0; e < DP; ++e) acc[e] = fmaf(p, vv[e], acc[e] * alpha);
+        attn_chunk<DP>(qv, kv, vv, ok, scale, m, l, acc);
     }
-    const float inv = 1.f / l;
-    float out = 0.f;
+    const float out = attn_finish<DP>(acc, l, D, lane);
+    if (lane < D) o[b * ldo + h * D + lane] = out;
+}
+
+// One-pass prompt prefill (include/charpt.h cg_decode_prefill_attn): every position t < P of a (b, h) is
+// one wave running k_decode_attn's chain with n = t + 1 keys, so its output row and the cache are what P
+// per-token steps leave, bit for bit.  A block of QB waves owns positions t0 .. t0 + QB - 1 of one (b, h):
+// it copies their K / V rows into the [B, H, Tmax, D] caches, and every 64-key chunk up to its last
+// position is staged in LDS once (all 64 QB threads: float i = tid + 64 QB r of the chunk's 64 D, row
+// i / D of the source at k + (b P + j) stride_kv + h D; the next chunk's loads issued before the current
+// chunk's arithmetic) and read by all QB waves -- P^2 / (2 QB) K / V rows per (b, h) instead of P^2 / 2.
+// LDS rows are DP + 1 floats apart: lane l reads row l, conflict-free for every D.  Keys past P are
+// staged as zeros; a lane whose key is past its wave's own position takes a zero V row, as
+// k_decode_attn_rows' lanes past n do (p is 0 there).  A wave skips the chunks past its position and a
+// wave past P computes nothing, but both meet every barrier of the block's chunk loop.
+// Work item bh * ceil(P / QB) + block-of-positions, XCD-contiguous: a (b, h)'s blocks share one L2.
+template <int DP, int QB>
+__global__ __launch_bounds__(64 * QB) void k_decode_prefill_attn(
+    const float* __restrict__ q, int64_t stride_q, const float* __restrict__ k, const float* __restrict__ v,
+    int64_t stride_kv, int64_t B, int64_t P, int64_t H, int64_t D, int64_t Tmax, float scale,
+    float* __restrict__ kc, float* __restrict__ vc, float* __restrict__ o, int64_t stride_o) {
+    constexpr int NT = 64 * QB, R = (64 * DP + NT - 1) / NT, DS = DP + 1;
+    __shared__ float ks[64 * DS], vs[64 * DS];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t nqb = (P + QB - 1) / QB;
+    const int64_t item = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
+    const int64_t bh = item / nqb, t0 = (item - bh * nqb) * QB;
+    const int64_t b = bh / H, h = bh - b * H;
+    const int64_t t = t0 + w;                      // this wave's position
+    const int64_t n = t < P ? t + 1 : 0;           // its keys 0..n-1 (0: a wave past the prompt)
+    const float* Kb = k + b * P * stride_kv + h * D;
+    const float* Vb = v + b * P * stride_kv + h * D;
+    if (n > 0 && lane < D) {                       // the cache rows of the block's positions: exact copies
+        const int64_t dst = ((b * H + h) * Tmax + t) * D + lane;
+        kc[dst] = Kb[t * stride_kv + lane];
+        vc[dst] = Vb[t * stride_kv + lane];
+    }
+    if (!q) return;                                // block-uniform: the cache-write-only form
+    float qv[DP], acc[DP];
 #pragma unroll
     for (int e = 0; e < DP; ++e) {
-        if (e < D) {   // wave-uniform
-            const float t = wave_sum_dpp(acc[e]);
-            out = lane == e ? t * inv : out;
+        qv[e] = n > 0 && e < D ? q[(b * P + t) * stride_q + h * D + e] : 0.f;
+        acc[e] = 0.f;
+    }
+    const int64_t nblock = (t0 + QB < P ? t0 + QB : P);   // keys the block's last position sees
+    const int cnt = 64 * (int)D;
+    int row[R], col[R];                            // float tid + NT r of a chunk: (row, e), row 64 = past it
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = tid + NT * r;
+        row[r] = i < cnt ? i / (int)D : 64;
+        col[r] = i < cnt ? i - row[r] * (int)D : 0;
+    }
+    float kr[R], vr[R];
+    auto load = [&](int64_t c0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int64_t j = c0 + row[r];
+            const bool in = row[r] < 64 && j < P;
+            kr[r] = in ? Kb[j * stride_kv + col[r]] : 0.f;
+            vr[r] = in ? Vb[j * stride_kv + col[r]] : 0.f;
+        }
+    };
+    float m = -INFINITY, l = 0.f;
+    load(0);
+    for (int64_t c0 = 0; c0 < nblock; c0 += 64) {   // block-uniform trip count
+        __syncthreads();   // every wave has read the previous chunk's rows
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (row[r] < 64) {
+                ks[row[r] * DS + col[r]] = kr[r];
+                vs[row[r] * DS + col[r]] = vr[r];
+            }
+        }
+        __syncthreads();
+        if (c0 + 64 < nblock) load(c0 + 64);
+        if (c0 < n) {      // wave-uniform: the chunk holds keys of this wave's query
+            const bool ok = c0 + lane < n;
+            float kv[DP], vv[DP];
+#pragma unroll
+            for (int e = 0; e < DP; ++e) {
+                kv[e] = e < D ? ks[lane * DS + e] : 0.f;
+                vv[e] = ok && e < D ? vs[lane * DS + e] : 0.f;
+            }
+            attn_chunk<DP>(qv, kv, vv, ok, scale, m, l, acc);
         }
     }
-    if (lane < D) o[b * ldo + h * D + lane] = out;
+    if (n == 0) return;
+    const float out = attn_finish<DP>(acc, l, D, lane);
+    if (lane < D) o[(b * P + t) * stride_o + h * D + lane] = out;
 }
 
 // (x, v) ahead of (best, bi) in torch.argmax's order: NaN counts as the maximum, the lower index
@@ -519,6 +615,21 @@ __device__ __forceinline__ float row_logprob(const float* __restrict__ row, int 
     return (row[tok] - m) - logf(s);
 }
 
+// The log-probs of a one-pass prefill (include/charpt.h cg_decode_logprob_rows): one wave per logits row
+// b P + t, logprob[b, t + 1] = row_logprob of idx[b, t + 1] -- what k_decode_emit stores for that column
+// when the row holds these logits.
+__global__ __launch_bounds__(256) void k_decode_logprob_rows(const float* __restrict__ logits, int64_t stride_logits,
+                                                             int V, int64_t B, int64_t P,
+                                                             const int64_t* __restrict__ idx, int64_t stride_idx,
+                                                             float* __restrict__ logprob, int64_t stride_logprob) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= B * P) return;   // wave-uniform
+    const int64_t b = r / P, t = r - b * P;
+    const float lp = row_logprob(logits + r * stride_logits, V, idx[b * stride_idx + t + 1], lane);
+    if (lane == 0) logprob[b * stride_logprob + t + 1] = lp;
+}
+
 // The ragged engine's per-row epilogue (include/charpt.h cg_decode_emit): one block per row, 64 threads
 // (modes 0 and 1: choose_plain) or 256 (mode 2: choose_filtered), so an emitted token is the old
 // samplers' by construction.  Every branch below is block-uniform; thread 0 does all the stores.
@@ -611,6 +722,54 @@ extern "C" int cg_decode_attn(const float* q, int64_t ldq, const float* k, const
         k_decode_attn<64><<<ceil_div(B * H, 4), 256, 0, (hipStream_t)stream>>>(q, ldq, k, v, sb, sh, sj, B, H, D,
                                                                                len_dev, nkeys, scale, o, ldo);
     CG_LAUNCH_CHECK("cg_decode_attn");
+    return CG_OK;
+}
+
+extern "C" int cg_decode_prefill_attn(const float* q, int64_t stride_q, const float* k, const float* v,
+                                      int64_t stride_kv, int64_t B, int64_t P, int64_t H, int64_t D, int64_t Tmax,
+                                      float scale, float* kcache, float* vcache, float* o, int64_t stride_o,
+                                      void* stream) {
+    // positions (waves) per block: 8, or 4 at DP = 64, whose 192 row registers per lane leave room for
+    // one wave per SIMD
+    const int QB = D <= 24 ? 8 : 4;
+    CG_REQUIRE(B > 0 && H > 0 && D > 0 && Tmax > 0, "cg_decode_prefill_attn: bad sizes (B = %lld, H = %lld, D = %lld, "
+               "Tmax = %lld)", (long long)B, (long long)H, (long long)D, (long long)Tmax);
+    CG_REQUIRE(D <= 64, "cg_decode_prefill_attn: D = %lld, needs D <= 64", (long long)D);
+    CG_REQUIRE(P >= 1 && P <= Tmax, "cg_decode_prefill_attn: P = %lld is outside 1..Tmax = %lld", (long long)P,
+               (long long)Tmax);
+    CG_REQUIRE(k && v && kcache && vcache, "cg_decode_prefill_attn: null k / v / kcache / vcache");
+    CG_REQUIRE((q == nullptr) == (o == nullptr), "cg_decode_prefill_attn: q and o must both be given or both be NULL");
+    CG_REQUIRE(stride_kv >= H * D && (!q || (stride_q >= H * D && stride_o >= H * D)),
+               "cg_decode_prefill_attn: a row stride is below H * D = %lld", (long long)(H * D));
+    CG_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)o) & 3) == 0,
+               "cg_decode_prefill_attn: a pointer is not 4-B aligned");
+    const int64_t nblk = B * H * ((P + QB - 1) / QB);
+    CG_REQUIRE(nblk < (1ll << 31), "cg_decode_prefill_attn: B * H * ceil(P / %d) = %lld blocks is above the grid limit", QB,
+               (long long)nblk);
+    if (D <= 24)
+        k_decode_prefill_attn<24, 8><<<(unsigned)nblk, 64 * 8, 0, (hipStream_t)stream>>>(
+            q, stride_q, k, v, stride_kv, B, P, H, D, Tmax, scale, kcache, vcache, o, stride_o);
+    else
+        k_decode_prefill_attn<64, 4><<<(unsigned)nblk, 64 * 4, 0, (hipStream_t)stream>>>(
+            q, stride_q, k, v, stride_kv, B, P, H, D, Tmax, scale, kcache, vcache, o, stride_o);
+    CG_LAUNCH_CHECK("cg_decode_prefill_attn");
+    return CG_OK;
+}
+
+extern "C" int cg_decode_logprob_rows(const float* logits, int64_t stride_logits, int64_t V, int64_t B, int64_t P,
+                                      const int64_t* idx, int64_t stride_idx, float* logprob, int64_t stride_logprob,
+                                      void* stream) {
+    CG_REQUIRE(B > 0 && P > 0 && B * P < (1ll << 32), "cg_decode_logprob_rows: bad sizes (B = %lld, P = %lld)", (long long)B,
+               (long long)P);
+    CG_REQUIRE(V >= 1 && V <= INT_MAX, "cg_decode_logprob_rows: V = %lld is outside 1..%d", (long long)V, INT_MAX);
+    CG_REQUIRE(stride_logits >= V, "cg_decode_logprob_rows: stride_logits = %lld is below V = %lld",
+               (long long)stride_logits, (long long)V);
+    CG_REQUIRE(stride_idx > P && stride_logprob > P, "cg_decode_logprob_rows: stride_idx = %lld / stride_logprob = %lld "
+               "do not hold column P = %lld", (long long)stride_idx, (long long)stride_logprob, (long long)P);
+    CG_REQUIRE(logits && idx && logprob, "cg_decode_logprob_rows: null pointer");
+    k_decode_logprob_rows<<<ceil_div(B * P, 4), 256, 0, (hipStream_t)stream>>>(logits, stride_logits, (int)V, B, P, idx,
+                                                                              stride_idx, logprob, stride_logprob);
+    CG_LAUNCH_CHECK("cg_decode_logprob_rows");
     return CG_OK;
 }
 

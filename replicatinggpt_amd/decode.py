@@ -31,8 +31,18 @@ computed as:
   the pad token and the sampling settings are device buffers rewritten per call.
 
 The current length lives in a device int64, so each phase's step is one static-shape hipGraph
-captured once and replayed per token (prefill of a longer prompt replays the phase-1 graph without
-sampling).  fp32 models give the reference's greedy stream (tests/test_gpu_model.py).
+captured once and replayed per token.
+
+Prompt prefill: an fp32 engine runs the prompt positions every row shares (``prefill_plan``) in one
+eager forward over B x Pn rows (``_prefill_pass``: the engine's own row operations, whose values do
+not depend on the row count, around ``cg_decode_prefill_attn``, which gives each position
+``cg_decode_attn``'s arithmetic; with log-probs ``cg_decode_logprob_rows`` scores those columns) and
+continues with the per-token steps from there -- the caches, tokens and log-probabilities are bit for
+bit those of a per-token prefill, so a row still does not depend on its batch-mates.  Prompts below
+``prefill_min`` positions, bf16 engines (their GEMM kernel, and so the order of every sum, is chosen
+by the row count) and ``CHARPT_PREFILL_PASS=0`` replay the phase-1 graph without sampling once per
+prompt position instead.  ``prefill_stats`` tells which happened in the last call.  fp32 models give
+the reference's greedy stream (tests/test_gpu_model.py).
 """
 import os
 
@@ -47,11 +57,35 @@ DECODE_ROWS = os.environ.get("CHARPT_DECODE_ROWS", "1") == "1"
 # CHARPT_LAST_KV_SPLIT=0: the window step's last block computes Q for every row too (A/B)
 LAST_KV_SPLIT = os.environ.get("CHARPT_LAST_KV_SPLIT", "1") == "1"
 EMIT_GREEDY, EMIT_DRAW, EMIT_FILTERED = 0, 1, 2   # cg_decode_emit's mode
+# CHARPT_PREFILL_PASS=0: every prompt position through its own phase-1 step, as before the one-pass prefill (A/B)
+PREFILL_PASS = os.environ.get("CHARPT_PREFILL_PASS", "1") == "1"
+# the shortest run of prompt positions the pass takes over from the per-token steps: the pass is a dozen eager
+# launches per layer (1.6 ms at the C5 shape however short the prompt), a step one graph replay (0.25 ms), and
+# a 16-token prompt is the shortest measured at which the pass wins by more than both spreads
+# (profiles/prefill_ab.txt)
+PREFILL_MIN = 15
+# the pass's logits workspace: at most this many floats per row chunk of the scoring head
+PREFILL_LOGITS_CAP = 1 << 26
+
+
+def prefill_plan(pmin, T, logprobs, prefill_min):
+    """How many prompt positions 0..Pn-1 the one-pass prefill covers (0: no pass) for a batch whose
+    shortest prompt has ``pmin`` tokens, on a window of ``T``.  Without log-probs the pass replaces the
+    no-head prefill steps: Pn = pmin - 1, and only when the first decided column pmin is still in phase
+    1 (pmin <= T).  With log-probs it also scores the columns it covers (1..Pn) and stops one position
+    early, Pn = min(pmin - 1, T) - 1: every such column n has n + 1 < pmin <= limit[b], so no row can end
+    there and cg_decode_emit's rule for it is the log-prob store alone.  Below ``prefill_min`` positions
+    the per-token steps stay."""
+    if logprobs:
+        Pn = min(pmin - 1, T) - 1
+    else:
+        Pn = pmin - 1 if pmin <= T else 0
+    return Pn if Pn >= max(1, prefill_min) else 0
 
 
 class DecodeEngine:
     def __init__(self, model, batch, max_len, greedy=True, seed=0, use_graph=True, filtered=False, ragged=False,
-                 logprobs=False):
+                 logprobs=False, prefill_pass=None, prefill_min=None):
         cfg = model.config
         if filtered and greedy and not ragged:
             raise ValueError("DecodeEngine: filtered sampling and greedy exclude each other")
@@ -80,6 +114,12 @@ class DecodeEngine:
         self.logits = torch.empty((B, self.V), dtype=torch.float32, device=dev)
         self.use_graph = use_graph and dev.type == "cuda"
         self.g1 = self.g1_prefill = self.g2 = None
+        # one-pass prefill: fp32 only -- a bf16 GEMM's kernel, and with it the k order of every sum, is
+        # chosen by the row count, so a pass over B * Pn rows could not give the per-token steps' bits
+        on = PREFILL_PASS if prefill_pass is None else bool(prefill_pass)
+        self.prefill_pass = on and self.act == torch.float32 and self.D <= 64
+        self.prefill_min = PREFILL_MIN if prefill_min is None else int(prefill_min)
+        self.prefill_stats = {"passes": 0, "positions": 0, "step_replays": 0}   # of the last call
         self.ragged = bool(ragged)
         if self.ragged:
             # everything complete() varies per call is device memory cg_decode_emit reads when it runs
@@ -218,6 +258,45 @@ class DecodeEngine:
         self._sample()
         ops.counter_add(self.len, 1)
 
+    # -- one-pass prefill: prompt positions 0..Pn-1 of every row in one forward --------------------
+    def _prefill_pass(self, Pn, score):
+        """What Pn phase-1 steps from len = 1 leave, bit for bit: the K/V cache rows 0..Pn-1 of every
+        layer, len = Pn + 1 and, with ``score``, logprob[:, 1..Pn].  The engine's own fp32 row operations at
+        M = B Pn rows (each row's value is independent of the row count) around cg_decode_prefill_attn,
+        which gives every position k_decode_attn's chain.  Eager, once per call: Pn varies per call.
+        Without ``score`` nothing reads the last layer's output, so it computes ln1 + the K / V columns only."""
+        B, C, H, D, T = self.B, self.C, self.H, self.D, self.T
+        M = B * Pn
+        x = torch.empty((M, C), dtype=torch.float32, device=self.dev)
+        ops.embed_fwd(self.idx[:, :Pn].contiguous(), self._b("wte"), self._b("wpe"), x)
+        for l in range(self.L):
+            wq = self._w(f"{l}.qkv")   # [3C, C]: Q rows, then K, then V
+            if l == self.L - 1 and not score:
+                kv = torch.empty((M, 2 * C), dtype=torch.float32, device=self.dev)
+                self._ln_linear(x, f"{l}.ln1", wq[C:], kv)
+                ops.decode_prefill_attn(None, kv[:, :C], kv[:, C:], Pn, self.scale, self.kc[l], self.vc[l], None)
+                break
+            qkv = torch.empty((M, 3 * C), dtype=torch.float32, device=self.dev)
+            self._ln_linear(x, f"{l}.ln1", wq, qkv)
+            o = torch.empty((M, C), dtype=torch.float32, device=self.dev)
+            ops.decode_prefill_attn(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], Pn, self.scale, self.kc[l],
+                                    self.vc[l], o)
+            x2 = torch.empty((M, C), dtype=torch.float32, device=self.dev)
+            Fn.linear_fwd(o, self._w(f"{l}.proj_w"), x2, "bias_resid", bias=self._b(f"{l}.proj_b"), resid=x)
+            x = self._ffn_tail(l, x2)
+        if score:
+            # ln_f + lm_head + the log-prob of the next prompt token, whole batch rows per chunk
+            nb = max(1, PREFILL_LOGITS_CAP // (Pn * self.V))
+            lm_w, lm_b = self._R("lm_w").operand(self.act), self._b("lm_b")
+            for b0 in range(0, B, nb):
+                b1 = min(B, b0 + nb)
+                logits = torch.empty(((b1 - b0) * Pn, self.V), dtype=torch.float32, device=self.dev)
+                self._ln_linear(x[b0 * Pn:b1 * Pn], "lnf", lm_w, logits, bias=lm_b)
+                ops.decode_logprob_rows(logits, Pn, self.idx[b0:b1], self.logprob[b0:b1])
+        self.len.fill_(Pn + 1)
+        self.prefill_stats["passes"] += 1
+        self.prefill_stats["positions"] += Pn
+
     # -- driver ------------------------------------------------------------------------------
     def _graph(self, fn):
         if not self.use_graph:
@@ -269,14 +348,20 @@ class DecodeEngine:
                 self.seed.fill_(int(seed))
             self.idx[:, :L0].copy_(idx)
             total = L0 + max_new_tokens
+            self.prefill_stats = {"passes": 0, "positions": 0, "step_replays": 0}
+            Pn = prefill_plan(L0, self.T, False, self.prefill_min) if self.prefill_pass else 0
             if L0 > self.T:                        # prompt longer than the window: phase 2 only
                 self.len.fill_(L0)
+                n = L0
+            elif Pn:                               # positions 0..L0-2 in one pass
+                self._prefill_pass(Pn, False)
                 n = L0
             else:
                 self.len.fill_(1)
                 n = 1                              # tokens present, mirrored on the host
             while n < L0:                          # prompt prefill: positions 0..L0-2
                 self.g1_prefill.replay() if self.g1_prefill else run1p()
+                self.prefill_stats["step_replays"] += 1
                 n += 1
             while n < total:
                 if n <= self.T:
@@ -355,15 +440,24 @@ class DecodeEngine:
             self.idx[:, :Lmax].copy_(idx)
             if want_lp:
                 self.logprob.zero_()
+            self.prefill_stats = {"passes": 0, "positions": 0, "step_replays": 0}
             steps = 0
             n = n0
             if n0 < total:                             # else no column is left to decide
+                Pn = prefill_plan(pmin, self.T, want_lp, self.prefill_min) if self.prefill_pass else 0
                 if n0 > self.T:                        # every prompt longer than the window: phase 2 only
                     self.len.fill_(n0)
+                elif Pn:
+                    # positions 0..Pn-1 in one pass; with log-probs it decides columns 1..Pn too (each
+                    # counts as a head step), else it ends where the no-head steps would: len = n0
+                    self._prefill_pass(Pn, want_lp)
+                    if want_lp:
+                        n, steps = Pn + 1, Pn
                 else:
                     self.len.fill_(1)
                     for _ in range(1, n0):             # no output needed yet: the no-head prefill step
                         g1p.replay() if g1p else self._step1(False)
+                        self.prefill_stats["step_replays"] += 1
                 while n < total:
                     if n <= self.T:
                         g1.replay() if g1 else self._step1(True)

@@ -722,6 +722,52 @@ def decode_emit(logits: Tensor, emit_mode: int, params: Optional[Tensor], seed: 
                                     L.ptr(pad), L.ptr(idx), idx.stride(0), L.ptr(logprob), _s(logits)), "decode_emit")
 
 
+@_op("decode_prefill_attn", ("kcache", "vcache", "o"))
+def decode_prefill_attn(q: Optional[Tensor], k: Tensor, v: Tensor, P: int, scale: float, kcache: Tensor,
+                        vcache: Tensor, o: Optional[Tensor]) -> None:
+    """One-pass prompt prefill of a layer (include/charpt.h cg_decode_prefill_attn): q, k, v [B * P, H * D]
+    float32 views (unit column stride; k and v one row stride) of the QKV rows of B x P positions; the
+    [B, H, Tmax, D] caches get rows t < P, o [B * P, H * D] what decode_attn gives position t with t + 1
+    keys, bit for bit.  q = o = None: the cache rows only."""
+    if kcache.dim() != 4 or kcache.dtype != torch.float32 or not kcache.is_contiguous() or \
+            vcache.dtype != torch.float32 or tuple(vcache.shape) != tuple(kcache.shape) or not vcache.is_contiguous():
+        raise ValueError("decode_prefill_attn: kcache and vcache must be dense float32 [B, H, Tmax, D] of one shape")
+    B, H, Tmax, D = kcache.shape
+    if (q is None) != (o is None):
+        raise ValueError("decode_prefill_attn: q and o must both be given or both be None")
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (B * P, H * D)
+                              or t.stride(1) != 1 or t.device != kcache.device):
+            raise ValueError(f"decode_prefill_attn: {name} must be float32 [B * P, H * D] = [{B * P}, {H * D}] with "
+                             f"unit column stride on {kcache.device}")
+    if k.stride(0) != v.stride(0):
+        raise ValueError("decode_prefill_attn: k and v must have one row stride")
+    L.check(L.load().cg_decode_prefill_attn(L.ptr(q), 0 if q is None else q.stride(0), L.ptr(k), L.ptr(v), k.stride(0),
+                                            B, P, H, D, Tmax, scale, L.ptr(kcache), L.ptr(vcache), L.ptr(o),
+                                            0 if o is None else o.stride(0), _s(k)), "decode_prefill_attn")
+
+
+@_op("decode_logprob_rows", ("logprob",))
+def decode_logprob_rows(logits: Tensor, P: int, idx: Tensor, logprob: Tensor) -> None:
+    """logprob[b, t + 1] = log softmax(logits[b * P + t])[idx[b, t + 1]] for t < P, decode_emit's log-prob bit
+    for bit (include/charpt.h cg_decode_logprob_rows): logits float32 [B * P, V], idx int64 and logprob
+    float32 [B, > P], unit column strides."""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("decode_logprob_rows: logits must be float32 [B * P, V] with unit column stride")
+    if idx.dtype != torch.int64 or idx.dim() != 2 or idx.stride(1) != 1:
+        raise ValueError("decode_logprob_rows: idx must be int64 [B, > P] with unit column stride")
+    B = idx.shape[0]
+    if P < 1 or logits.shape[0] != B * P or idx.shape[1] <= P:
+        raise ValueError(f"decode_logprob_rows: logits {tuple(logits.shape)} and idx {tuple(idx.shape)} do not hold "
+                         f"B x P = {B} x {P} rows and column P")
+    if logprob.dtype != torch.float32 or logprob.dim() != 2 or logprob.stride(1) != 1 or logprob.shape[0] != B or \
+            logprob.shape[1] <= P:
+        raise ValueError("decode_logprob_rows: logprob must be float32 [B, > P] with unit column stride")
+    L.check(L.load().cg_decode_logprob_rows(L.ptr(logits), logits.stride(0), logits.shape[1], B, P, L.ptr(idx),
+                                            idx.stride(0), L.ptr(logprob), logprob.stride(0), _s(logits)),
+            "decode_logprob_rows")
+
+
 # ---------------------------------------------------------------------------------------
 @_op("adamw", ("p", "m", "v", "p_bf16"))
 def adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, p_bf16: Optional[Tensor], lr: float, beta1: float, beta2: float,
