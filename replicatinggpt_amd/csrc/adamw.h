@@ -1,12 +1,12 @@
 // charpt: AdamW element arithmetic (torch.optim.AdamW, GPT1.py:218,233), shared by the AdamW kernels
-// (ce_adamw.hip) and the AdamW jobs the persistent GEMM's free blocks run (gemm_common.h red_tail).
+// (adamw.hip) and the AdamW jobs the persistent GEMM's free blocks run (gemm_common.h red_tail).
 #pragma once
 #include <math.h>
 
 #include "common.h"
 
 namespace cg {
-extern int g_adamw_mode;   // cg_set_tuning("adamw_mode", 0..5): cg_adamw's kernel form, 0 = by size (ce_adamw.hip)
+extern int g_adamw_mode;   // cg_set_tuning("adamw_mode", 0..5): cg_adamw's kernel form, 0 = by size (adamw.hip)
 
 // The fp32 arithmetic of torch/optim/adam.py _single_tensor_adam (decoupled decay) as torch's CPU
 // kernels round it:

@@ -54,10 +54,10 @@ void enqueue_partials(const PartJob& j, hipStream_t st);
 
 // defer.hip holds host code only; the kernels its flushes launch:
 void launch_reduce_partials_multi(const PartJobs& jobs, hipStream_t st);   // reduce.hip
-int adamw_job_launch(const AdamJob& j, hipStream_t st);                    // ce_adamw.hip
+int adamw_job_launch(const AdamJob& j, hipStream_t st);                    // adamw.hip
 int adamw_segments_launch(float* p, const float* g, float* m, float* v, bf16_t* pb, const int64_t* segs, int nseg,
                           double lr, double beta1, double beta2, double eps, double wd, const int64_t* step,
-                          hipStream_t st);                                 // ce_adamw.hip
+                          hipStream_t st);                                 // adamw.hip
 
 // cg_set_tuning knobs (defer.hip; g_red_side is with take_pending_reduces in gemm_common.h)
 extern int g_adam_per_launch;      // AdamW jobs one launch's free blocks take (0 = MAX_ADAM)

@@ -1,6 +1,6 @@
 // charpt deferred work (defer.h; include/charpt.h "Deferred work"): the per-(device, stream) queues of
 // split-K reduces, AdamW updates and column-sum reduces, what a persistent GEMM launch takes from them
-// and what cg_flush_deferred launches.  Host code only: the kernels are reduce.hip's and ce_adamw.hip's.
+// and what cg_flush_deferred launches.  Host code only: the kernels are reduce.hip's and adamw.hip's.
 #include <map>
 
 #include "defer.h"

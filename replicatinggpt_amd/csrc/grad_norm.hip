@@ -1,7 +1,7 @@
 // charpt: global-norm gradient clipping over the flat gradient buffer (torch.nn.utils.clip_grad_norm_
 // with norm_type 2): the L2 norm and the clip coefficient on the device, and the in-place scale for
 // hand-written loops.  The training step multiplies by the coefficient inside AdamW instead
-// (ce_adamw.hip cg_adamw_dyn), so clipping costs one 4 B/param read pass.
+// (adamw.hip cg_adamw_dyn), so clipping costs one 4 B/param read pass.
 #include <math.h>
 
 #include "common.h"

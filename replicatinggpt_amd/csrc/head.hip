@@ -261,29 +261,28 @@ extern "C" int64_t cg_head_workspace(int64_t M, int64_t V) {
     return (nb * (V > 1 ? V : 1) + 64) * (int64_t)sizeof(float);
 }
 
-extern "C" int cg_head_fwd(const void* a, const void* wpad, int64_t wpad_rows, const float* bias,
-                           const int64_t* targets, float* logits, float* lse, float* loss, void* workspace,
-                           int64_t M, int64_t C, int64_t V, void* stream) {
-    CG_REQUIRE(M > 0 && C > 0 && V > 0, "cg_head_fwd: empty problem");
-    CG_REQUIRE(M % 16 == 0 && C % 32 == 0, "cg_head_fwd: needs M %% 16 == 0 and C %% 32 == 0 (M=%lld C=%lld)",
-               (long long)M, (long long)C);
-    CG_REQUIRE(V <= 128 && wpad_rows >= ((V + 15) / 16) * 16, "cg_head_fwd: V=%lld needs wpad_rows >= %lld (<=128)",
+// cg_head_fwd / cg_head_fwd_masked: the requirements they share and the one VT x KS dispatch.  `who`: the
+// entry point's name, for the messages; part / ignore / cpart: k_head_fwd's loss_part / ignore / cnt_part
+template <bool MASKED>
+static int head_fwd_launch(const char* who, const void* a, const void* wpad, int64_t wpad_rows, const float* bias,
+                           const int64_t* targets, float* logits, float* lse, float* part, int64_t ignore, int* cpart,
+                           int64_t M, int64_t C, int64_t V, hipStream_t st) {
+    CG_REQUIRE(M > 0 && C > 0 && V > 0, "%s: empty problem", who);
+    CG_REQUIRE(M % 16 == 0 && C % 32 == 0, "%s: needs M %% 16 == 0 and C %% 32 == 0 (M=%lld C=%lld)", who, (long long)M,
+               (long long)C);
+    CG_REQUIRE(V <= 128 && wpad_rows >= ((V + 15) / 16) * 16, "%s: V=%lld needs wpad_rows >= %lld (<=128)", who,
                (long long)V, (long long)(((V + 15) / 16) * 16));
-    CG_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)wpad & 15) == 0, "cg_head_fwd: operands must be 16-B aligned");
-    CG_REQUIRE(!targets || (loss && workspace), "cg_head_fwd: targets need loss and workspace");
-    hipStream_t st = (hipStream_t)stream;
+    CG_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)wpad & 15) == 0, "%s: operands must be 16-B aligned", who);
     const int nb = ceil_div(M, HEAD_ROWS);
-    float* part = targets ? (float*)workspace : nullptr;
-    const int VT = (int)((V + 15) / 16);
-#define HFK(vt, ks)                                                                                          \
-    k_head_fwd<vt, ks, false><<<nb, 256, 0, st>>>((const bf16_t*)a, C, (const bf16_t*)wpad, bias, (int)V, targets, \
-                                                  logits, lse, part, M, 0, nullptr)
+#define HFK(vt, ks)                                                                                                 \
+    k_head_fwd<vt, ks, MASKED><<<nb, 256, 0, st>>>((const bf16_t*)a, C, (const bf16_t*)wpad, bias, (int)V, targets, \
+                                                   logits, lse, part, M, ignore, cpart)
 #define HF(vt)                          \
     if (C == 128) HFK(vt, 4);           \
     else if (C == 384) HFK(vt, 12);     \
     else if (C == 768) HFK(vt, 24);     \
     else HFK(vt, 0)
-    switch (VT) {
+    switch ((int)((V + 15) / 16)) {
         case 1: HF(1); break;
         case 2: HF(2); break;
         case 3: HF(3); break;
@@ -295,8 +294,36 @@ extern "C" int cg_head_fwd(const void* a, const void* wpad, int64_t wpad_rows, c
     }
 #undef HF
 #undef HFK
-    if (targets) k_head_loss_final<<<1, 256, 0, st>>>(part, nb, 1.f / (float)M, loss);
+    return CG_OK;
+}
+
+extern "C" int cg_head_fwd(const void* a, const void* wpad, int64_t wpad_rows, const float* bias,
+                           const int64_t* targets, float* logits, float* lse, float* loss, void* workspace,
+                           int64_t M, int64_t C, int64_t V, void* stream) {
+    CG_REQUIRE(!targets || (loss && workspace), "cg_head_fwd: targets need loss and workspace");
+    hipStream_t st = (hipStream_t)stream;
+    float* part = targets ? (float*)workspace : nullptr;
+    if (int rc = head_fwd_launch<false>("cg_head_fwd", a, wpad, wpad_rows, bias, targets, logits, lse, part, 0, nullptr,
+                                        M, C, V, st))
+        return rc;
+    if (targets) k_head_loss_final<<<1, 256, 0, st>>>(part, ceil_div(M, HEAD_ROWS), 1.f / (float)M, loss);
     CG_LAUNCH_CHECK("cg_head_fwd");
+    return CG_OK;
+}
+
+// cg_head_bwd_ex / cg_head_bwd_masked: k_head_bwd and the bias gradient's reduce of its partials
+template <bool MASKED>
+static int head_bwd_launch(const char* who, const float* logits, const float* lse, const int64_t* targets,
+                           const float* g_loss, float g_mult, const float* g_logits, void* dl, int64_t KP, float* db,
+                           int db_accumulate, void* workspace, int64_t M, int64_t V, int64_t ignore, const float* norm,
+                           int flags, hipStream_t st) {
+    const int nb = ceil_div(M, HEAD_ROWS);
+    k_head_bwd<MASKED><<<nb, 256, 0, st>>>(logits, lse, targets, g_loss, g_mult, g_logits, (int)V, M, (bf16_t*)dl,
+                                           (int)KP, (float*)workspace, ignore, norm);
+    if (db)   // CG_DEFER: queued on the stream's deferral queue (functional.DEFER, db a flat gradient slot)
+        reduce_partials_deferrable((const float*)workspace, nb, V, db, nullptr, nullptr, V, db_accumulate, 0,
+                                   flags & CG_DEFER, st);
+    CG_LAUNCH_CHECK(who);
     return CG_OK;
 }
 
@@ -307,15 +334,8 @@ extern "C" int cg_head_bwd_ex(const float* logits, const float* lse, const int64
     CG_REQUIRE((flags & ~CG_DEFER) == 0, "cg_head_bwd_ex: unknown flags %#x", flags);
     CG_REQUIRE(ld_dl % 8 == 0 && ld_dl >= V && ld_dl <= 128, "cg_head_bwd: ld_dl must be a multiple of 8 in [V, 128]");
     CG_REQUIRE(!targets || g_loss, "cg_head_bwd: targets need g_loss");
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = ceil_div(M, HEAD_ROWS);
-    k_head_bwd<false><<<nb, 256, 0, st>>>(logits, lse, targets, g_loss, g_mult, g_logits, (int)V, M, (bf16_t*)dl,
-                                          (int)ld_dl, (float*)workspace, 0, nullptr);
-    if (db)   // CG_DEFER: queued on the stream's deferral queue (functional.DEFER, db a flat gradient slot)
-        reduce_partials_deferrable((const float*)workspace, nb, V, db, nullptr, nullptr, V, db_accumulate, 0,
-                                   flags & CG_DEFER, st);
-    CG_LAUNCH_CHECK("cg_head_bwd");
-    return CG_OK;
+    return head_bwd_launch<false>("cg_head_bwd", logits, lse, targets, g_loss, g_mult, g_logits, dl, ld_dl, db,
+                                  db_accumulate, workspace, M, V, 0, nullptr, flags, (hipStream_t)stream);
 }
 
 extern "C" int cg_head_bwd(const float* logits, const float* lse, const int64_t* targets, const float* g_loss,
@@ -337,14 +357,6 @@ extern "C" int cg_head_fwd_masked(const void* a, const void* wpad, int64_t wpad_
                                   const int64_t* targets, int64_t ignore_index, float* logits, float* lse,
                                   float* loss, float* norm, void* workspace, int64_t M, int64_t C, int64_t V,
                                   void* stream) {
-    CG_REQUIRE(M > 0 && C > 0 && V > 0, "cg_head_fwd_masked: empty problem");
-    CG_REQUIRE(M % 16 == 0 && C % 32 == 0,
-               "cg_head_fwd_masked: needs M %% 16 == 0 and C %% 32 == 0 (M=%lld C=%lld)", (long long)M, (long long)C);
-    CG_REQUIRE(V <= 128 && wpad_rows >= ((V + 15) / 16) * 16,
-               "cg_head_fwd_masked: V=%lld needs wpad_rows >= %lld (<=128)", (long long)V,
-               (long long)(((V + 15) / 16) * 16));
-    CG_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)wpad & 15) == 0,
-               "cg_head_fwd_masked: operands must be 16-B aligned");
     CG_REQUIRE(targets && logits && lse && loss && norm && workspace,
                "cg_head_fwd_masked: targets, logits, lse, loss, norm and workspace are required");
     CG_REQUIRE(M < ((int64_t)1 << 24), "cg_head_fwd_masked: the count of valid rows must be exact in fp32 (M < 2^24)");
@@ -352,27 +364,9 @@ extern "C" int cg_head_fwd_masked(const void* a, const void* wpad, int64_t wpad_
     const int nb = ceil_div(M, HEAD_ROWS);
     float* part = (float*)workspace;
     int* cpart = (int*)workspace + nb;
-    const int VT = (int)((V + 15) / 16);
-#define HFK(vt, ks)                                                                                                \
-    k_head_fwd<vt, ks, true><<<nb, 256, 0, st>>>((const bf16_t*)a, C, (const bf16_t*)wpad, bias, (int)V, targets, \
-                                                 logits, lse, part, M, ignore_index, cpart)
-#define HF(vt)                          \
-    if (C == 128) HFK(vt, 4);           \
-    else if (C == 384) HFK(vt, 12);     \
-    else if (C == 768) HFK(vt, 24);     \
-    else HFK(vt, 0)
-    switch (VT) {
-        case 1: HF(1); break;
-        case 2: HF(2); break;
-        case 3: HF(3); break;
-        case 4: HF(4); break;
-        case 5: HF(5); break;
-        case 6: HF(6); break;
-        case 7: HF(7); break;
-        default: HF(8); break;
-    }
-#undef HF
-#undef HFK
+    if (int rc = head_fwd_launch<true>("cg_head_fwd_masked", a, wpad, wpad_rows, bias, targets, logits, lse, part,
+                                       ignore_index, cpart, M, C, V, st))
+        return rc;
     k_head_loss_final_masked<<<1, 256, 0, st>>>(part, cpart, nb, loss, norm);
     CG_LAUNCH_CHECK("cg_head_fwd_masked");
     return CG_OK;
@@ -387,13 +381,6 @@ extern "C" int cg_head_bwd_masked(const float* logits, const float* lse, const i
     CG_REQUIRE(KP % 8 == 0 && KP >= V && KP <= 128, "cg_head_bwd_masked: KP must be a multiple of 8 in [V, 128]");
     CG_REQUIRE(logits && lse && targets && g_loss && norm && dl && workspace,
                "cg_head_bwd_masked: logits, lse, targets, g_loss, norm, dl and workspace are required");
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = ceil_div(M, HEAD_ROWS);
-    k_head_bwd<true><<<nb, 256, 0, st>>>(logits, lse, targets, g_loss, 0.f, g_logits, (int)V, M, (bf16_t*)dl, (int)KP,
-                                         (float*)workspace, ignore_index, norm);
-    if (db)
-        reduce_partials_deferrable((const float*)workspace, nb, V, db, nullptr, nullptr, V, db_accumulate, 0,
-                                   flags & CG_DEFER, st);
-    CG_LAUNCH_CHECK("cg_head_bwd_masked");
-    return CG_OK;
+    return head_bwd_launch<true>("cg_head_bwd_masked", logits, lse, targets, g_loss, 0.f, g_logits, dl, KP, db,
+                                 db_accumulate, workspace, M, V, ignore_index, norm, flags, (hipStream_t)stream);
 }

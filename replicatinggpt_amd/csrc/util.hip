@@ -316,7 +316,7 @@ const Knob KNOBS[] = {
     {"attn_variant", &g_attn_variant, AB_LO(0), AB_HI(2)},
     {"attn_bwd_lpt", &g_attn_bwd_lpt, 0, 1},       // attention_d64.hip k_attn_bwd_d64r: merged resident backward order (1 = dK/dV first)
     {"decode_attn_rows", &g_decode_attn_rows, 0, 1},   // decode.hip: the coalesced-chunk phase-1 decode attention
-    {"adamw_mode", &g_adamw_mode, 0, 5},           // ce_adamw.hip: cg_adamw's kernel form, 0 = by size
+    {"adamw_mode", &g_adamw_mode, 0, 5},           // adamw.hip: cg_adamw's kernel form, 0 = by size
     {"ln_rl", &g_ln_rl, 0, 2},   // layernorm.hip: backward rows' next loads before the current stores (2: also at C = 768)
     {"ln_nt", &g_ln_nt, ANY_LO, ANY_HI},           // layernorm.hip: the backward's non-temporal streams (-1 automatic, 0..3)
     {"ln_pf", &g_ln_pf, ANY_LO, ANY_HI},           // layernorm.hip: next row's loads before the current row

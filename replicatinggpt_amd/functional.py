@@ -667,12 +667,9 @@ def attention_fwd(qkv, B, T, H, D, out, scale, p, seed, rng_call, site, premask=
         mask = torch.empty(ops.attn_mask_bytes(B, H, T) // 8, dtype=torch.int64, device=qkv.device)
     if "skip_attn" in WHATIF:
         return lse, mask
-    if seg is not None:
-        ops.attn_fwd_seg(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), out, out.stride(0), lse, float(scale), float(p),
-                         int(seed), rng_call, int(site), mask, seg[0], seg[1], ready)
-        return lse, mask
-    ops.attn_fwd(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), out, out.stride(0), lse, float(scale), float(p),
-                 int(seed), rng_call, int(site), mask, ready)
+    op, segs = (ops.attn_fwd, ()) if seg is None else (ops.attn_fwd_seg, tuple(seg))
+    op(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), out, out.stride(0), lse, float(scale), float(p), int(seed),
+       rng_call, int(site), mask, *segs, ready)
     return lse, mask
 
 
@@ -708,13 +705,9 @@ def attention_bwd(qkv, B, T, H, D, o, do, lse, scale, p, seed, rng_call, site, m
     ws = torch.empty(ops.attn_bwd_workspace(B, T, H, D) // 4, dtype=torch.float32, device=qkv.device)
     if "skip_attn" in WHATIF:
         return dqkv
-    if seg is not None:
-        ops.attn_bwd_seg(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), o, o.stride(0), do, do.stride(0), lse, dqkv,
-                         dqkv.stride(0), float(scale), float(p), int(seed), rng_call, int(site), mask, ws, seg[0],
-                         seg[1], delta)
-        return dqkv
-    ops.attn_bwd(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), o, o.stride(0), do, do.stride(0), lse, dqkv,
-                 dqkv.stride(0), float(scale), float(p), int(seed), rng_call, int(site), mask, ws, delta)
+    op, segs = (ops.attn_bwd, ()) if seg is None else (ops.attn_bwd_seg, tuple(seg))
+    op(qkv, B, T, H, D, 0, d, 2 * d, qkv.stride(0), o, o.stride(0), do, do.stride(0), lse, dqkv, dqkv.stride(0),
+       float(scale), float(p), int(seed), rng_call, int(site), mask, ws, *segs, delta)
     return dqkv
 
 
@@ -781,19 +774,17 @@ class EmbeddingFn(torch.autograd.Function):
         gp, bp, fp = wpe_reg.grad_target()
         if gt is not None or gp is not None:
             ws = torch.empty(ops.embed_bwd_workspace(B, T, C, V) // 4, dtype=torch.float32, device=dx.device)
-            if ctx.seg is not None:
-                se = ctx.seg[1]
-                if bt != bp and gt is not None and gp is not None:
-                    ops.embed_bwd_seg(idx, se, dx.contiguous(), gt, None, bool(bt), ws)
-                    ops.embed_bwd_seg(idx, se, dx.contiguous(), None, gp[:T], bool(bp), ws)
-                else:
-                    ops.embed_bwd_seg(idx, se, dx.contiguous(), gt, gp[:T] if gp is not None else None,
-                                      bool(bt or bp), ws)
-            elif bt != bp and gt is not None and gp is not None:
-                ops.embed_bwd(idx, dx.contiguous(), gt, None, bool(bt), ws)
-                ops.embed_bwd(idx, dx.contiguous(), None, gp[:T], bool(bp), ws)
+            if ctx.seg is None:
+                def bwd(*args):
+                    ops.embed_bwd(idx, *args)
             else:
-                ops.embed_bwd(idx, dx.contiguous(), gt, gp[:T] if gp is not None else None, bool(bt or bp), ws)
+                def bwd(*args):
+                    ops.embed_bwd_seg(idx, ctx.seg[1], *args)
+            if bt != bp and gt is not None and gp is not None:   # one accumulate flag per call: one call each
+                bwd(dx.contiguous(), gt, None, bool(bt), ws)
+                bwd(dx.contiguous(), None, gp[:T], bool(bp), ws)
+            else:
+                bwd(dx.contiguous(), gt, gp[:T] if gp is not None else None, bool(bt or bp), ws)
             if gp is not None and not bp and T < gp.shape[0]:
                 gp[T:].zero_()  # positions beyond T get no gradient (overwrite mode)
         SIDE.join(dx.device)   # last node of the model backward: every gradient is final after this
@@ -1061,169 +1052,148 @@ class HeadLossFn(torch.autograd.Function):
     ``apply(x, targets, act, ln_w, ln_b, lm_w, lm_b, *params[, ignore_index])``: an int after the
     parameter tensors is F.cross_entropy's ``ignore_index`` -- targets equal to it add nothing to the
     loss or the gradients and the mean is over the others (the masked entry points of csrc/head.hip and
-    csrc/ce_adamw.hip; the normaliser stays on the device, saved for the backward).  Without it (or
-    with None) the unmasked kernels run, as they always did."""
+    csrc/ce.hip; the normaliser stays on the device, saved for the backward).  Without it, with None or
+    without targets the unmasked kernels run, as they always did.
+
+    One forward and one backward.  What differs between the plain path (cg_gemm + csrc/ce.hip) and the
+    bf16 fast path (csrc/head.hip + K-padded MFMA GEMMs, _head_fused_ok) is a function each way below:
+    ``_head_*_fwd`` gives (logits [M, V], lse, loss or None, norm or None), ``_head_*_bwd`` gives the
+    gradient of ln_f's output and the lm_head weight's and bias's finishers (Region.grad_target)."""
 
     @staticmethod
     def forward(ctx, x, targets, act, ln_w, ln_b, lm_w, lm_b, *params):
-        ignore_index = None
-        if params and not isinstance(params[-1], torch.Tensor):
-            ignore_index, params = params[-1], params[:-1]
-            ctx.ignore_slot = True
-        ctx.ignore_index = None if (ignore_index is None or targets is None) else int(ignore_index)
+        ctx.ignore_slot = bool(params) and not isinstance(params[-1], torch.Tensor)
+        ignore = params[-1] if ctx.ignore_slot else None
+        ctx.ignore_index = ignore = None if (ignore is None or targets is None) else int(ignore)
         B, T, C = x.shape
-        M = B * T
+        M, V = B * T, lm_w.master.shape[0]
         x2 = x.reshape(M, C)
         pre = pre_ln(x, ln_w, ln_b, act)   # ln_f from the last FFN GEMM's epilogue
         a, mean, rstd = pre if pre is not None else layernorm(x2, ln_w.master, ln_b.master, act)
-        V = lm_w.master.shape[0]
         ctx.fused = _head_fused_ok(act, lm_w, M, C, V)
         ctx.in_link = _link_of(x)
-        if ctx.fused:
-            return HeadLossFn._fused_forward(ctx, x, x2, targets, act, a, mean, rstd, (ln_w, ln_b, lm_w, lm_b))
-        logits = torch.empty((M, V), dtype=torch.float32, device=x.device)
-        linear_fwd(a, lm_w.operand(act), logits, "bias", bias=lm_b.master)
-        lse = torch.empty(M, dtype=torch.float32, device=x.device)
         ctx.regs, ctx.shape, ctx.act = (ln_w, ln_b, lm_w, lm_b), (B, T, C), act
         ctx.set_materialize_grads(False)
-        if targets is None:
-            ctx.save_for_backward(x2, a, mean, rstd, logits, lse)
-            ctx.has_targets = False
-            return logits.view(B, T, V)
-        t1 = targets.reshape(M)
-        loss_rows = torch.empty(M, dtype=torch.float32, device=x.device)
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        if ctx.ignore_index is not None:
+        t1 = None if targets is None else targets.reshape(M)
+        if ignore is not None:
             t1 = t1.contiguous()
-            ops.ce_fwd_masked(logits, t1, ctx.ignore_index, loss_rows, lse)
-            norm = torch.empty(2, dtype=torch.float32, device=x.device)
-            ws = torch.empty(ops.ce_mean_masked_workspace(M) // 4, dtype=torch.float32, device=x.device)
-            ops.ce_mean_masked(loss_rows, t1, ctx.ignore_index, loss, norm, ws)
-            ctx.save_for_backward(x2, a, mean, rstd, logits, lse, t1, norm)
-            ctx.has_targets = True
-            return logits, loss
-        ops.ce_fwd(logits, t1, loss_rows, lse)
-        ws = torch.empty(1024, dtype=torch.float32, device=x.device)
-        ops.sum_scaled(loss_rows, 1.0 / M, loss, ws)
-        ctx.save_for_backward(x2, a, mean, rstd, logits, lse, t1)
-        ctx.has_targets = True
-        return logits, loss
+        logits, lse, loss, norm = (_head_fused_fwd if ctx.fused else _head_plain_fwd)(a, lm_w, lm_b, act, t1, ignore)
+        ctx.save_for_backward(x2, a, mean, rstd, logits, lse, t1, norm)
+        return logits.view(B, T, V) if targets is None else (logits, loss)
 
     @staticmethod
     def backward(ctx, *grads):
         ln_w, ln_b, lm_w, lm_b = ctx.regs
         B, T, C = ctx.shape
-        act = ctx.act
-        M = B * T
-        norm = None
-        if ctx.has_targets:
-            if ctx.ignore_index is not None:
-                x2, a, mean, rstd, logits, lse, t1, norm = ctx.saved_tensors
-            else:
-                x2, a, mean, rstd, logits, lse, t1 = ctx.saved_tensors
-            g_logits, g_loss = grads
-        else:
-            x2, a, mean, rstd, logits, lse = ctx.saved_tensors
-            g_logits, g_loss = grads[0], None
-        V = logits.shape[-1]
-        tail = (None,) if getattr(ctx, "ignore_slot", False) else ()   # the ignore_index argument's slot
-        if ctx.fused:
-            return HeadLossFn._fused_backward(ctx, x2, a, mean, rstd, logits, lse, t1 if ctx.has_targets else None,
-                                              g_logits, g_loss, norm) + tail
-        dl = torch.empty((M, V), dtype=torch.float32, device=x2.device)
-        if g_loss is not None:
-            if norm is not None:
-                ops.ce_bwd_masked(logits, t1, ctx.ignore_index, lse, g_loss.reshape(1).float().contiguous(), norm, dl,
-                                  None)
-            else:
-                ops.ce_bwd(logits, t1, lse, g_loss.reshape(1).float().contiguous(), 1.0 / M, dl, None)
-            if g_logits is not None:
-                dl.add_(g_logits.reshape(M, V))
-        else:
-            dl.copy_(g_logits.reshape(M, V))
-        dl_op = dl if act == torch.float32 else to_act(dl, act)
-        g, beta, f_lw = lm_w.grad_target()
-        if g is not None:
-            linear_wgrad(dl_op, a, g, beta, g is lm_w.slot)
-        g, beta, f_lb = lm_b.grad_target()
-        if g is not None:
-            colsum_into(dl, g, beta)
-        da = torch.empty((M, C), dtype=act, device=x2.device)
-        linear_dgrad(dl_op, lm_w.operand(act), da)
+        x2, a, mean, rstd, logits, lse, t1, norm = ctx.saved_tensors
+        g_logits, g_loss = grads if t1 is not None else (grads[0], None)
+        da, f_lw, f_lb = (_head_fused_bwd if ctx.fused else _head_plain_bwd)(
+            a, lm_w, lm_b, ctx.act, logits, lse, t1, norm, ctx.ignore_index, g_logits, g_loss)
         dx, _, f_ln = layernorm_bwd(da, x2, ln_w, ln_b, mean, rstd, link=ctx.in_link)
-        return (dx.view(B, T, C), None, None, None, None, None, None, *f_ln, *f_lw(), *f_lb()) + tail
+        return (dx.view(B, T, C), None, None, None, None, None, None, *f_ln, *f_lw(), *f_lb(),
+                *((None,) if ctx.ignore_slot else ()))   # the ignore_index argument's slot
 
-    # -- bf16 fast path: cg_head_fwd/bwd + K-padded MFMA GEMMs (csrc/head.hip) -------------
-    @staticmethod
-    def _fused_forward(ctx, x, x2, targets, act, a, mean, rstd, regs):
-        ln_w, ln_b, lm_w, lm_b = regs
-        B, T, C = x.shape
-        M, V = B * T, lm_w.master.shape[0]
-        wpad = lm_w.padded[0]
-        logits = torch.empty((M, V), dtype=torch.float32, device=x.device)
-        lse = torch.empty(M, dtype=torch.float32, device=x.device)
-        ctx.regs, ctx.shape, ctx.act = regs, (B, T, C), act
-        ctx.set_materialize_grads(False)
-        if targets is None:
-            ops.head_fwd(a, wpad, lm_b.master, None, logits, lse, None, None)
-            ctx.save_for_backward(x2, a, mean, rstd, logits, lse)
-            ctx.has_targets = False
-            return logits.view(B, T, V)
-        t1 = targets.reshape(M)
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        if ctx.ignore_index is not None:
-            t1 = t1.contiguous()
-            norm = torch.empty(2, dtype=torch.float32, device=x.device)
-            ws = torch.empty(ops.head_masked_workspace(M, V) // 4, dtype=torch.float32, device=x.device)
-            ops.head_fwd_masked(a, wpad, lm_b.master, t1, ctx.ignore_index, logits, lse, loss, norm, ws)
-            ctx.save_for_backward(x2, a, mean, rstd, logits, lse, t1, norm)
-            ctx.has_targets = True
-            return logits, loss
-        ws = torch.empty(ops.head_workspace(M, V) // 4, dtype=torch.float32, device=x.device)
+
+def _head_plain_fwd(a, lm_w, lm_b, act, t1, ignore):
+    M, V, dev = a.shape[0], lm_w.master.shape[0], a.device
+    logits = torch.empty((M, V), dtype=torch.float32, device=dev)
+    linear_fwd(a, lm_w.operand(act), logits, "bias", bias=lm_b.master)
+    lse = torch.empty(M, dtype=torch.float32, device=dev)
+    if t1 is None:
+        return logits, lse, None, None
+    loss_rows = torch.empty(M, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    if ignore is None:
+        ops.ce_fwd(logits, t1, loss_rows, lse)
+        ws = torch.empty(1024, dtype=torch.float32, device=dev)
+        ops.sum_scaled(loss_rows, 1.0 / M, loss, ws)
+        return logits, lse, loss, None
+    ops.ce_fwd_masked(logits, t1, ignore, loss_rows, lse)
+    norm = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = torch.empty(ops.ce_mean_masked_workspace(M) // 4, dtype=torch.float32, device=dev)
+    ops.ce_mean_masked(loss_rows, t1, ignore, loss, norm, ws)
+    return logits, lse, loss, norm
+
+
+def _head_plain_bwd(a, lm_w, lm_b, act, logits, lse, t1, norm, ignore, g_logits, g_loss):
+    M, V = logits.shape
+    dl = torch.empty((M, V), dtype=torch.float32, device=a.device)
+    if g_loss is not None:
+        g1 = g_loss.reshape(1).float().contiguous()
+        if norm is not None:
+            ops.ce_bwd_masked(logits, t1, ignore, lse, g1, norm, dl, None)
+        else:
+            ops.ce_bwd(logits, t1, lse, g1, 1.0 / M, dl, None)
+        if g_logits is not None:
+            dl.add_(g_logits.reshape(M, V))
+    else:
+        dl.copy_(g_logits.reshape(M, V))
+    dl_op = dl if act == torch.float32 else to_act(dl, act)
+    g, beta, f_lw = lm_w.grad_target()
+    if g is not None:
+        linear_wgrad(dl_op, a, g, beta, g is lm_w.slot)
+    g, beta, f_lb = lm_b.grad_target()
+    if g is not None:
+        colsum_into(dl, g, beta)
+    da = torch.empty(a.shape, dtype=act, device=a.device)
+    linear_dgrad(dl_op, lm_w.operand(act), da)
+    return da, f_lw, f_lb
+
+
+# -- bf16 fast path: cg_head_fwd/bwd + K-padded MFMA GEMMs (csrc/head.hip) -------------
+def _head_fused_fwd(a, lm_w, lm_b, act, t1, ignore):
+    M, V, dev = a.shape[0], lm_w.master.shape[0], a.device
+    wpad = lm_w.padded[0]
+    logits = torch.empty((M, V), dtype=torch.float32, device=dev)
+    lse = torch.empty(M, dtype=torch.float32, device=dev)
+    if t1 is None:
+        ops.head_fwd(a, wpad, lm_b.master, None, logits, lse, None, None)
+        return logits, lse, None, None
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    if ignore is None:
+        ws = torch.empty(ops.head_workspace(M, V) // 4, dtype=torch.float32, device=dev)
         ops.head_fwd(a, wpad, lm_b.master, t1, logits, lse, loss, ws)
-        ctx.save_for_backward(x2, a, mean, rstd, logits, lse, t1)
-        ctx.has_targets = True
-        return logits, loss
+        return logits, lse, loss, None
+    norm = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = torch.empty(ops.head_masked_workspace(M, V) // 4, dtype=torch.float32, device=dev)
+    ops.head_fwd_masked(a, wpad, lm_b.master, t1, ignore, logits, lse, loss, norm, ws)
+    return logits, lse, loss, norm
 
-    @staticmethod
-    def _fused_backward(ctx, x2, a, mean, rstd, logits, lse, t1, g_logits, g_loss, norm=None):
-        ln_w, ln_b, lm_w, lm_b = ctx.regs
-        B, T, C = ctx.shape
-        M, V = logits.shape
-        wpad, gpad = lm_w.padded
-        KP = wpad.shape[0]
-        dl = torch.empty((M, KP), dtype=torch.bfloat16, device=x2.device)
-        gb, beta_b, f_lb = lm_b.grad_target()
-        masked = norm is not None and g_loss is not None   # no loss gradient: dl = g_logits, nothing to mask
-        ws_bytes = ops.head_masked_workspace(M, V) if masked else ops.head_workspace(M, V)
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x2.device)
-        gl = None if g_logits is None else g_logits.reshape(M, V).float().contiguous()
-        if g_loss is None:
-            t1 = None
-        # the lm_head bias gradient's column-sum reduce joins DEFER's multi-job flush when it targets the slot
-        with DEFER.partials(ws) if (gb is not None and gb is lm_b.slot) else contextlib.nullcontext(False) as queued:
-            if masked:
-                ops.head_bwd_masked(logits, lse, t1, ctx.ignore_index, g_loss.reshape(1).float().contiguous(), norm, gl,
-                                    dl, gb, bool(beta_b), ws, queued)
+
+def _head_fused_bwd(a, lm_w, lm_b, act, logits, lse, t1, norm, ignore, g_logits, g_loss):
+    M, V = logits.shape
+    C, dev = a.shape[1], a.device
+    wpad, gpad = lm_w.padded
+    KP = wpad.shape[0]
+    dl = torch.empty((M, KP), dtype=torch.bfloat16, device=dev)
+    gb, beta_b, f_lb = lm_b.grad_target()
+    masked = norm is not None and g_loss is not None   # no loss gradient: dl = g_logits, nothing to mask
+    ws = torch.empty((ops.head_masked_workspace if masked else ops.head_workspace)(M, V) // 4, dtype=torch.float32,
+                     device=dev)
+    gl = None if g_logits is None else g_logits.reshape(M, V).float().contiguous()
+    g1 = None if g_loss is None else g_loss.reshape(1).float().contiguous()
+    # the lm_head bias gradient's column-sum reduce joins DEFER's multi-job flush when it targets the slot
+    with DEFER.partials(ws) if (gb is not None and gb is lm_b.slot) else contextlib.nullcontext(False) as queued:
+        if masked:
+            ops.head_bwd_masked(logits, lse, t1, ignore, g1, norm, gl, dl, gb, bool(beta_b), ws, queued)
+        else:
+            ops.head_bwd(logits, lse, t1 if g_loss is not None else None, g1, 1.0 / M, gl, dl, gb, bool(beta_b), ws,
+                         queued)
+    g, beta, f_lw = lm_w.grad_target()
+    if g is not None:
+        if g.data_ptr() == lm_w.slot.data_ptr():
+            with SIDE.run(dev, dl, a):
+                linear_wgrad(dl, a, gpad, beta, True)   # rows >= V get exact zeros (dl pad columns are 0)
+        else:
+            tmp = torch.empty((KP, C), dtype=torch.float32, device=dev)
+            linear_wgrad(dl, a, tmp, 0.0)
+            if beta:
+                g.add_(tmp[:V])
             else:
-                ops.head_bwd(logits, lse, t1, None if g_loss is None else g_loss.reshape(1).float().contiguous(),
-                             1.0 / M, gl, dl, gb, bool(beta_b), ws, queued)
-        g, beta, f_lw = lm_w.grad_target()
-        if g is not None:
-            if g.data_ptr() == lm_w.slot.data_ptr():
-                with SIDE.run(x2.device, dl, a):
-                    linear_wgrad(dl, a, gpad, beta, True)   # rows >= V get exact zeros (dl pad columns are 0)
-            else:
-                tmp = torch.empty((KP, C), dtype=torch.float32, device=x2.device)
-                linear_wgrad(dl, a, tmp, 0.0)
-                if beta:
-                    g.add_(tmp[:V])
-                else:
-                    g.copy_(tmp[:V])
-        da = torch.empty((M, C), dtype=torch.bfloat16, device=x2.device)
-        linear_dgrad(dl, wpad, da)
-        dx, _, f_ln = layernorm_bwd(da, x2, ln_w, ln_b, mean, rstd, link=ctx.in_link)
-        return (dx.view(B, T, C), None, None, None, None, None, None, *f_ln, *f_lw(), *f_lb())
+                g.copy_(tmp[:V])
+    da = torch.empty((M, C), dtype=torch.bfloat16, device=dev)
+    linear_dgrad(dl, wpad, da)
+    return da, f_lw, f_lb
 
 
 def _head_fused_ok(act, lm_w, M, C, V):

@@ -48,7 +48,7 @@ WHICH ROUNDINGS u COUNTS (by kernel, with the place in replicatinggpt_amd/csrc/)
   attention generic bf16          attention_generic.hip: fp32 inside, bf16 stores: u = 2^-9.
   attention fp32                  attention_f32.hip / attention_generic.hip: u = 2^-24 with the
                                   conditioning of P in S (expf(s scale - lse) in fp32).
-  cg_ce_fwd / cg_ce_bwd           ce_adamw.hip k_ce_fwd / k_ce_bwd: expf / logf in fp32, u = 2^-24.
+  cg_ce_fwd / cg_ce_bwd           ce.hip k_ce_fwd / k_ce_bwd: expf / logf in fp32, u = 2^-24.
   cg_head_fwd                     head.hip: logits fp32 MFMA accumulation (u = 2^-24); lse and the
                                   loss from those logits with __expf / __logf (u = 2^-24).
   cg_head_bwd[_ex]                head.hip k_head_bwd: dl is stored bf16 (pack_bf2): u = 2^-9; db
