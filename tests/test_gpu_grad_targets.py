@@ -24,6 +24,10 @@ blocks.1.ln2.weight = g(B) alone; torch 0.999106).  A norm error e means a cosin
 so the 0.999 rule is an absolute e < 4.5e-2 and these parameters are close to it: micro-batch B ALONE
 gives blocks.0.ln2.weight e_c 4.64e-2 / cosine 0.998924 (torch 4.36e-2 / 0.999050).  No scenario below
 expects that tensor alone -- B enters in sums, and bit for bit in scenario 3.
+
+Every bf16 run here takes every fast branch (build() asserts it).  The bf16 fallbacks -- generic GEMMs and
+attention, the plain head, weight gradients that decline slabs and deferral, the ring attention -- run
+inside a model in tests/test_gpu_bf16_offpath.py.
 """
 import functools
 
