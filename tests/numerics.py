@@ -10,7 +10,7 @@ module holds the three things the tests share.
 DATA PROFILES.  Functions of a torch.Generator that return CPU tensors (so test_cpu_numerics.py can
 assert each profile's stated property): `unit` is what the parity tests use and serves as control;
 `outlier`, `offset`, `flat` (GEMM / LayerNorm / reductions), `peaked`, `sink`, `shifted`, `spiked`
-(attention), `confident`, `wrong`, `offset` (cross entropy and head).
+(attention), `confident`, `wrong`, `offset`, `certain` (cross entropy, head and log-probabilities).
 
 BUDGETS.  For an output element let S be the sum of the absolute values of the terms that add up to
 it: the reference formula evaluated in fp64 with every operand replaced by its absolute value and
@@ -40,7 +40,18 @@ WHICH ROUNDINGS u COUNTS (by kernel, with the place in replicatinggpt_amd/csrc/)
   cg_layernorm_bwd / _ex / _rows + _reduce   layernorm.hip k_ln_bwd: fp32 throughout, u = 2^-24 for
                                   dx, dw, db; the GradLink copy is bf16(keep ? dx / (1 - p) : 0) of
                                   the written dx (bitwise), its column sums fp32 (u = 2^-24).
-  cg_linear_rows_f32 with ln      rows_f32.hip: fp32 LayerNorm and fp32 products, u = 2^-24.
+  cg_linear_rows_f32, cg_decode_qkv_f32, cg_ffn_fwd_f32   rows_f32.hip (and gemm_f32.hip k_gemm_f32r at
+                                  M <= 2048): the fp32 LayerNorm of ln_fwd.h, fp32 fmaf products, the fp32
+                                  epilogue; the FFN's hidden activations stay fp32 registers: u = 2^-24
+                                  everywhere (linear_ln_budget, ffn_budget).  The cache rows
+                                  cg_decode_qkv_f32 appends are copies (bitwise).
+  cg_decode_attn, cg_decode_prefill_attn   decode.hip attn_chunk / attn_finish: the score an fp32 fmaf
+                                  chain times scale, __expf of fp32 differences against the running
+                                  maximum of 64-key chunks, alpha = __expf(m - m_new) on l and acc, fp32
+                                  fmaf accumulation, one * (1 / l): u = 2^-24 with the conditioning of P
+                                  in S (attn_budget fp32_cond), as the fp32 training attention.
+  cg_decode_logprob_rows, cg_decode_emit step 4   decode.hip row_logprob: (x_t - m) - logf(sum __expf(x_v
+                                  - m)), fp32 lane-strided sums: u = 2^-24 (logprob_budget).
   attention bf16 D = 64           attention_d64_tile.h: softmax_pack packs P = exp2(s c - m) to bf16
   (resident and ring)             before the PV product and the matrix-core row sums, dq_group_tile /
                                   dkdv_tile pack dS = P (dP - delta) and P to bf16 (pack16), outputs
@@ -450,18 +461,55 @@ def attn_plain(q, k, v, dO, scale, keep=None, dtype=BF16, round_p=False):
             "dv": rnd(torch.einsum("bhts,bthd->bshd", Pd, dO), dtype)}
 
 
+def decode_attn_plain(q, k, v, scale, chunk=64):
+    """The decode path's attention in plain fp32 torch: row t is the query at position t against keys
+    0..t, as an online softmax over chunks of `chunk` keys in the statistics order of decode.hip's
+    attn_chunk -- per chunk m_new = max(m, chunk max), alpha = exp(m - m_new), p = exp(s - m_new),
+    l = l alpha + sum p, acc = acc alpha + p v, and o = acc (1 / l) at the end.  Written from the
+    mathematics (the dot products and chunk sums in torch's own order); q, k, v [B, T, H, D] already
+    rounded to fp32.  Returns o [B, T, H, D]."""
+    q, k, v = (t.float() for t in (q, k, v))
+    B, T, H, D = q.shape
+    s = (torch.einsum("bthd,bshd->bhts", q, k) * np.float32(scale)).masked_fill(~_causal(T), -math.inf)
+    m = torch.full((B, H, T, 1), -math.inf)
+    l = torch.zeros(B, H, T, 1)
+    acc = torch.zeros(B, H, T, D)
+    for c0 in range(0, T, chunk):
+        sc = s[..., c0:c0 + chunk]
+        m_new = torch.maximum(m, sc.max(-1, keepdim=True).values)
+        alpha = torch.exp(m - m_new)
+        p = torch.exp(sc - m_new)
+        l = l * alpha + p.sum(-1, keepdim=True)
+        acc = acc * alpha + torch.einsum("bhts,bshd->bhtd", p, v[:, c0:c0 + chunk])
+        m = m_new
+    return (acc * (1.0 / l)).permute(0, 2, 1, 3).contiguous()
+
+
+def decode_attn_rho_plain(q, k, v, scale, ref, S):
+    """rho of the two plain orders (torch's whole-row softmax, the chunk-64 online softmax) per row t:
+    [T] tensors of the larger, so that a run with n keys is judged against row n - 1's own figure and
+    the whole o against the maximum."""
+    z = torch.zeros_like(q)
+    out = None
+    for got in (attn_plain(q, k, v, z, scale, dtype=F32)["o"], decode_attn_plain(q, k, v, scale)):
+        r = torch.tensor([rho(got[:, t], ref[:, t], S[:, t], U32).value for t in range(q.shape[1])], dtype=F64)
+        out = r if out is None else torch.maximum(out, r)
+    return out
+
+
 # ---- cross entropy and the head --------------------------------------------------------------------------
 def ce_logits(g, rows, V, profile):
     """logits [rows, V] fp32 and targets.  unit: randn * 3.  Rows r % 4 == 3 stay unit in every profile.
     confident: the target logit is 30 above the largest other one; wrong: 30 below the smallest;
-    offset: every logit + 1e3."""
+    offset: every logit + 1e3; certain: confident with a margin of 100 (exp(-100) is below fp32's normal
+    range: every other weight underflows against the right maximum, and exp(+100) overflows against a wrong one)."""
     x = torch.randn(rows, V, generator=g) * 3
     tgt = torch.randint(0, V, (rows,), generator=g)
     hit = torch.arange(rows) % 4 != 3
-    if profile in ("confident", "wrong"):
+    if profile in ("confident", "wrong", "certain"):
         others = x.clone()
-        others[torch.arange(rows), tgt] = -math.inf if profile == "confident" else math.inf
-        new = others.max(1).values + 30 if profile == "confident" else others.min(1).values - 30
+        others[torch.arange(rows), tgt] = math.inf if profile == "wrong" else -math.inf
+        new = others.min(1).values - 30 if profile == "wrong" else others.max(1).values + (30 if profile == "confident" else 100)
         x[hit, tgt[hit]] = new[hit]
     elif profile == "offset":
         x[hit] += 1e3
@@ -497,6 +545,94 @@ def ce_plain(x, tgt, g=1.0, lse_in=None):
     lb = lse if lse_in is None else lse_in.float()
     return {"lse": lse, "loss": lse - x[torch.arange(rows), tgt],
             "dlogits": np.float32(g) * (torch.exp(x - lb[:, None]) - onehot)}
+
+
+def logprob_budget(x, tgt):
+    """(ref, S) of the decode path's log-probability of token tgt_r in row r, from the header's formula
+    (x_t - m) - log sum_v exp(x_v - m), m = max x: ref = x_t - lse; S = |x_t - m| + |lse - m| + 1.  The
+    two differences are the terms that are added (x_v - m of fp32 numbers within a factor 2 of each
+    other is exact, of others it carries u |x_v - m|, which the sum's weights exp(x_v - m) <= 1 damp
+    below u |lse - m| + u); the 1 is the sum's and the log's own rounding, relative errors of the sum
+    being absolute ones of its log.  Shift-invariant, as the contract is: adding a constant to a row
+    changes neither ref nor S, so on `offset` this is tighter than ce_budget's max|x| term."""
+    x = x.double()
+    r = torch.arange(x.shape[0])
+    m = x.max(1).values
+    lse = torch.logsumexp(x, 1)
+    xt = x[r, tgt]
+    return xt - lse, (xt - m).abs() + (lse - m).abs() + 1
+
+
+def logprob_plain(x, tgt, order="torch"):
+    """fp32: torch.log_softmax's own order, or ("formula") the header's formula term by term."""
+    x = x.float()
+    r = torch.arange(x.shape[0])
+    if order == "torch":
+        return torch.log_softmax(x, 1)[r, tgt]
+    m = x.max(1).values
+    return (x[r, tgt] - m) - torch.log(torch.exp(x - m[:, None]).sum(1))
+
+
+def logprob_rho_plain(x, tgt, ref, S):
+    return max(rho(logprob_plain(x, tgt, o), ref, S, U32).value for o in ("torch", "formula"))
+
+
+# ---- the fp32 inference rows (rows_f32.hip) ---------------------------------------------------------------
+def linear_ln_budget(a, lw, lb, W, bias=None, resid=None, relu=False, eps=EPS):
+    """(ref, S) of out = [resid +] act(a' W^T [+ bias]) with a' = LayerNorm(a; lw, lb) (lw given) or a' = a.
+    Every a'_k carries the error u S_LN,k of ln_fwd_budget's y (0 without the LayerNorm, where a' is an
+    operand) and |a'_k| <= S_LN,k, so the product's own roundings and the propagated ones are both
+    inside S = S_a' |W|^T + |bias| + |resid|, S_a' = S_LN or |a|.  ReLU is 1-Lipschitz: |relu(got) -
+    relu(ref)| <= |got - ref|, the same S serves and no decision rule is needed in a forward."""
+    if lw is not None:
+        y, Sy = ln_fwd_budget(a, lw, lb, eps)["y"]
+    else:
+        y, Sy = a.double(), a.double().abs()
+    ref, S = y @ W.double().t(), Sy @ W.double().abs().t()
+    if bias is not None:
+        ref, S = ref + bias.double(), S + bias.double().abs()
+    if relu:
+        ref = torch.relu(ref)
+    if resid is not None:
+        ref, S = ref + resid.double(), S + resid.double().abs()
+    return ref, S
+
+
+def linear_ln_rho_plain(a, lw, lb, W, ref, S, bias=None, resid=None, relu=False, eps=EPS):
+    """The larger rho of the fp32 product on both ln_fwd_plain orders (on a itself and in K chunks of 32
+    without the LayerNorm)."""
+    def tail(acc):
+        acc = acc if bias is None else acc + bias.float()
+        acc = torch.relu(acc) if relu else acc
+        return acc if resid is None else acc + resid.float()
+    if lw is None:
+        return gemm_rho_plain(a, W, ref, S, bias=bias, resid=resid, relu=relu)
+    return max(rho(tail(ln_fwd_plain(a, lw, lb, eps, order=o)[0] @ W.float().t()), ref, S, U32).value
+               for o in ("torch", "twopass"))
+
+
+def ffn_budget(a, lw, lb, W1, b1, W2, b2, resid, eps=EPS):
+    """(ref, S) of out = resid + relu(a' W1^T + b1) W2^T + b2, a' as in linear_ln_budget.
+    The hidden pre-activation z = a' W1^T + b1 carries u S_h, S_h = S_a' |W1|^T + |b1| (linear_ln_budget);
+    h = relu(z) carries no more (1-Lipschitz).  The second product sums the terms h_j W2_cj, each with
+    its own rounding u |h_ref,j| |W2_cj| and the propagated u S_h,j |W2_cj|, then b2 and resid:
+    S_out = |resid| + |b2| + (|h_ref| + S_h) |W2|^T."""
+    z, S_h = linear_ln_budget(a, lw, lb, W1, b1, eps=eps)
+    h = torch.relu(z)
+    ref = resid.double() + h @ W2.double().t() + b2.double()
+    S = resid.double().abs() + b2.double().abs() + (h.abs() + S_h) @ W2.double().abs().t()
+    return ref, S
+
+
+def ffn_rho_plain(a, lw, lb, W1, b1, W2, b2, resid, ref, S, eps=EPS):
+    out = 0.0
+    for o in ("torch", "twopass"):
+        y = ln_fwd_plain(a, lw, lb, eps, order=o)[0] if lw is not None else a.float()
+        got = resid.float() + (torch.relu(y @ W1.float().t() + b1.float()) @ W2.float().t() + b2.float())
+        out = max(out, rho(got, ref, S, U32).value)
+        if lw is None:
+            break
+    return out
 
 
 def head_operands(g, M, C, V, profile):

@@ -39,11 +39,16 @@ RAN_P = {}       # entry point -> layout-P cases that ran its kernel (the last t
 REFUSALS = []    # (case, message): every asserted CG_EINVAL
 FELL_BACK = []   # (case, reason): cases that keep check 1 only in place of check 2
 CASES = [0]
-# stride-taking entry points this file leaves to test_gpu_decode.py / test_gpu_sampling.py /
-# test_gpu_complete.py, which run them on padded rows
-ELSEWHERE = {"cg_linear_rows_f32", "cg_ffn_fwd_f32", "cg_decode_qkv_f32", "cg_decode_window", "cg_decode_embed",
-             "cg_decode_kv_append", "cg_decode_attn", "cg_decode_sample", "cg_decode_sample_filtered",
-             "cg_decode_emit"}
+# stride-taking entry points this file leaves to other files.  The three samplers: test_gpu_decode.py /
+# test_gpu_sampling.py / test_gpu_complete.py run them on padded rows with 50.0 planted past V and assert
+# that no other column is written.  cg_decode_prefill_attn and cg_decode_logprob_rows have their Box tests
+# (guard bands, const snapshots, NaN against zero prefill) in test_gpu_prefill.py, and the three
+# segment-masked attention calls (stride_* arguments too) in test_gpu_packed_footprint.py, which keeps its
+# own count of padded runs.
+ELSEWHERE = {"cg_decode_sample", "cg_decode_sample_filtered", "cg_decode_emit", "cg_decode_prefill_attn",
+             "cg_decode_logprob_rows", "cg_attn_fwd_seg", "cg_attn_fwd_seg_premasked", "cg_attn_bwd_seg"}
+MOVED_HERE = {"cg_linear_rows_f32", "cg_ffn_fwd_f32", "cg_decode_qkv_f32", "cg_decode_window", "cg_decode_embed",
+              "cg_decode_kv_append", "cg_decode_attn"}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -1195,24 +1200,259 @@ def test_grad_norm_and_scale(n, align):
     footprint("cg_scale_f32", make_scale, layouts=("T",))
 
 
+# ---- the inference path: decode.hip and rows_f32.hip ------------------------------------------------------------
+DEC_FORMS = ("cache-D21", "qkvrows-D21", "generic-D21", "cache-D64")
+
+
+def make_decode_attn(lay, form, fixed):
+    """cg_decode_attn, one query per (b, h) against n = 70 of Tmax = 128 keys; the K / V rows >= n are
+    NaN (const operands: the stale part of a cache).  cache-D21: tight key rows reach
+    k_decode_attn_rows<24>, padded ones (layouts P, O) its SJ form; qkvrows: K / V inside a window's qkv
+    rows (SJ); generic: decode_attn_rows 0, k_decode_attn<24>; cache-D64: k_decode_attn<64>."""
+    D_ = 64 if form.endswith("D64") else 21
+    B, H, Tmax, n = 3, 2, 128, 70
+    HD = H * D_
+    g = torch.Generator().manual_seed(21)
+    q = torch.randn(B, HD, generator=g)
+    K, V = torch.randn(B, H, Tmax, D_, generator=g), torch.randn(B, H, Tmax, D_, generator=g)
+    scale = f32(HD ** -0.5)
+    s = torch.einsum("bhd,bhjd->bhj", q.view(B, H, D_).double(), K[:, :, :n].double()) * scale
+    want = torch.einsum("bhj,bhjd->bhd", torch.softmax(s, -1), V[:, :, :n].double()).reshape(B, HD)
+    K[:, :, n:] = float("nan")
+    V[:, :, n:] = float("nan")
+    c = Call(f"cg_decode_attn[{lay} {form} {'nkeys' if fixed else 'len_dev'} n {n}]")
+    qb = c.cin("q", box(B, HD, F32, lay, 1), q)
+    ob = c.cout("o", box(B, HD, F32, lay, 2))
+    if form.startswith("qkvrows"):
+        rows = torch.cat([torch.randn(B, Tmax, HD, generator=g), K.permute(0, 2, 1, 3).reshape(B, Tmax, HD),
+                          V.permute(0, 2, 1, 3).reshape(B, Tmax, HD)], 2).reshape(B * Tmax, 3 * HD)
+        kv = c.cin("qkv rows", box(B * Tmax, 3 * HD, F32, lay, 3), rows)
+        kp, vp, sb, sh, sj = P(kv, HD), P(kv, 2 * HD), Tmax * kv.ld, D_, kv.ld
+    else:
+        kb = c.cin("k", box(B * H * Tmax, D_, F32, lay, 3), K.reshape(-1, D_))
+        vb = c.cin("v", box(B * H * Tmax, D_, F32, lay, 3), V.reshape(-1, D_))
+        kp, vp, sj = P(kb), P(vb), kb.ld
+        sh, sb = Tmax * sj, H * Tmax * sj
+    ln = c.keep = dev_i64(n)
+    c.launch = lambda: lib().cg_decode_attn(P(qb), qb.ld, kp, vp, sb, sh, sj, B, H, D_, None if fixed else P_t(ln),
+                                            n if fixed else 0, scale, P(ob), ob.ld, stream())
+    c.verify = lambda c_: _assert(relerr(ob.view, want) < 1e-5, (c_.name, relerr(ob.view, want)))
+    return c
+
+
+@pytest.mark.parametrize("fixed", [False, True], ids=["len_dev", "nkeys"])
+@pytest.mark.parametrize("form", DEC_FORMS)
+def test_decode_attn(form, fixed):
+    """The four dispatch forms in layouts T, P and O (the header states no alignment and takes any
+    strides): checks 1-5, the three layouts' bits equal (the kernels are bitwise twins)."""
+    assert tuning("decode_attn_rows", 0 if form.startswith("generic") else 1) == 0
+    try:
+        bits = footprint("cg_decode_attn", lambda lay: make_decode_attn(lay, form, fixed), layouts=("T", "P", "O"))
+        same_bits(bits["T"], bits["O"], f"cg_decode_attn {form}: layout T against layout O")
+    finally:
+        tuning("decode_attn_rows", 1)
+
+
+def test_decode_kv_append():
+    """The caches are in/out operands: only row len - 1 of every (b, h) changes, to the qkv row's bits."""
+    B, H, D_, Tmax, n = 3, 2, 21, 16, 8
+    HD = H * D_
+    g = torch.Generator().manual_seed(22)
+    qkv = torch.randn(B, 3 * HD, generator=g)
+    k0, v0 = torch.randn(B * H * Tmax, D_, generator=g), torch.randn(B * H * Tmax, D_, generator=g)
+
+    def make(lay):
+        c = Call(f"cg_decode_kv_append[{lay}]")
+        qb = c.cin("qkv", box(B, 3 * HD, F32, lay, 1), qkv)
+        kb = c.cio("kcache", Box(B * H * Tmax, D_, F32, offset_bytes=off(lay, F32), device=DEV), k0)
+        vb = c.cio("vcache", Box(B * H * Tmax, D_, F32, offset_bytes=off(lay, F32), device=DEV), v0)
+        ln = c.keep = dev_i64(n)
+        c.launch = lambda: lib().cg_decode_kv_append(P(qb), qb.ld, HD, 2 * HD, B, H, D_, Tmax, P_t(ln), P(kb), P(vb), stream())
+
+        def verify(c_):
+            for name, bx, init, col in (("k", kb, k0, HD), ("v", vb, v0, 2 * HD)):
+                want = init.clone().view(B, H, Tmax, D_)
+                want[:, :, n - 1] = qkv[:, col:col + HD].view(B, H, D_)
+                assert torch.equal(bx.view.cpu().view(I32), want.view(-1, D_).view(I32)), (c_.name, name)
+
+        c.verify = verify
+        return c
+
+    footprint("cg_decode_kv_append", make, layouts=("T", "P", "O"))
+
+
+@pytest.mark.parametrize("n", [5, 12, 20])
+def test_decode_window(n):
+    """out[b, j] = idx[b, max(0, len - T) + j] at len below, at and above T = 12; idx rows of 20 tokens."""
+    B, T, Lx = 3, 12, 20
+    idx = torch.randint(0, 65, (B, Lx), generator=torch.Generator().manual_seed(23))
+
+    def make(lay):
+        c = Call(f"cg_decode_window[{lay} len {n}]")
+        ib = c.cin("idx", box(B, Lx, I64, lay, 1, pad=3), idx)
+        ob = c.cout("out", Box(B, T, I64, offset_bytes=off(lay, I64), device=DEV))
+        ln = c.keep = dev_i64(n)
+        c.launch = lambda: lib().cg_decode_window(P(ib), ib.ld, B, T, P_t(ln), P(ob), stream())
+        start = max(0, n - T)
+        c.verify = lambda c_: _assert(torch.equal(ob.view.cpu(), idx[:, start:start + T]), c_.name)
+        return c
+
+    footprint("cg_decode_window", make, layouts=("T", "P", "O"))
+
+
+def test_decode_embed():
+    """x[b] = wte[idx[b, len - 1]] + wpe[len - 1], bit for bit."""
+    B, C, Vn, Tmax, n = 5, 126, 65, 16, 9
+    g = torch.Generator().manual_seed(24)
+    idx = torch.randint(0, Vn, (B, Tmax), generator=g)
+    wte, wpe = torch.randn(Vn, C, generator=g), torch.randn(Tmax, C, generator=g)
+
+    def make(lay):
+        c = Call(f"cg_decode_embed[{lay}]")
+        ib = c.cin("idx", box(B, Tmax, I64, lay, 1, pad=3), idx)
+        tb = c.cin("wte", Box(Vn, C, F32, offset_bytes=off(lay, F32), device=DEV), wte)
+        pb = c.cin("wpe", Box(Tmax, C, F32, offset_bytes=off(lay, F32), device=DEV), wpe)
+        xb = c.cout("x", Box(B, C, F32, offset_bytes=off(lay, F32), device=DEV))
+        ln = c.keep = dev_i64(n)
+        c.launch = lambda: lib().cg_decode_embed(P(ib), ib.ld, P(tb), P(pb), C, P_t(ln), P(xb), B, stream())
+        c.verify = lambda c_: _assert(torch.equal(xb.view.cpu(), wte[idx[:, n - 1]] + wpe[n - 1]), c_.name)
+        return c
+
+    footprint("cg_decode_embed", make, layouts=("T", "P", "O"))
+
+
+def _ln64(x, w, b, eps=1e-5):
+    x = x.double()
+    mu = x.mean(1, keepdim=True)
+    return (x - mu) / torch.sqrt(((x - mu) ** 2).mean(1, keepdim=True) + eps) * w.double() + b.double()
+
+
+@pytest.mark.parametrize("kind", ["store", "bias_relu", "bias_resid"])
+@pytest.mark.parametrize("ln", [True, False], ids=["ln", "noln"])
+@pytest.mark.parametrize("M", [33, 2050])
+def test_linear_rows_f32(M, ln, kind):
+    """cg_linear_rows_f32 on both sides of 2048 rows (k_gemm_f32r, k_linear_f32q), with and without the
+    LayerNorm.  Layout O: odd strides and a 4-B offset base are refused (the header: lda / ldw even, a / W
+    8-B aligned).  The header names no aliasing for this call, so resid and out stay apart."""
+    N, K = 70, 126
+    g = torch.Generator().manual_seed(25)
+    a = torch.randn(M, K, generator=g) * 2 + 0.5
+    W, bias, resid = torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g), torch.randn(M, N, generator=g)
+    lw, lb = torch.randn(K, generator=g) * 0.1 + 1, torch.randn(K, generator=g) * 0.1
+    want = (_ln64(a, lw, lb) if ln else a.double()) @ W.double().t()
+    if kind != "store":
+        want = want + bias.double()
+    want = torch.relu(want) if kind == "bias_relu" else want
+    want = want + resid.double() if kind == "bias_resid" else want
+
+    def make(lay):
+        c = Call(f"cg_linear_rows_f32[{lay} M {M} ln {int(ln)} {kind}]")
+        dense_a = ln and M > 2048 and lay == "P"        # the header: lda == K with the LayerNorm above 2048 rows
+        ab = c.cin("a", box(M, K, F32, lay, 0 if dense_a else 1), a)
+        wb = c.cin("w", box(N, K, F32, lay, 2), W)
+        lwb = c.cin("ln_w", vec(K, F32, lay), lw) if ln else None
+        lbb = c.cin("ln_b", vec(K, F32, lay), lb) if ln else None
+        bb = c.cin("bias", vec(N, F32, lay), bias) if kind != "store" else None
+        rb = c.cin("resid", box(M, N, F32, lay, 3), resid) if kind == "bias_resid" else None
+        ob = c.cout("out", box(M, N, F32, lay, 4))
+        c.launch = lambda: lib().cg_linear_rows_f32(M, N, K, P(ab), ab.ld, P(lwb), P(lbb), 1e-5, P(wb), wb.ld, P(bb),
+                                                    int(kind == "bias_relu"), P(rb), rb.ld if rb is not None else 0, P(ob), ob.ld,
+                                                    stream())
+        c.verify = lambda c_: _assert(relerr(ob.view, want) < 1e-5, (c_.name, relerr(ob.view, want)))
+        return c
+
+    footprint("cg_linear_rows_f32", make)
+    refused(make("O"), "cg_linear_rows_f32")
+
+
+@pytest.mark.parametrize("ln", [True, False], ids=["ln", "noln"])
+@pytest.mark.parametrize("M", [33, 300])
+def test_ffn_fwd_f32(M, ln):
+    """cg_ffn_fwd_f32 with out aliasing resid (an in/out operand), one block and three; layout O refused."""
+    C, Hh = 126, 504
+    g = torch.Generator().manual_seed(26)
+    a = torch.randn(M, C, generator=g) * 2 + 0.5
+    W1, b1 = torch.randn(Hh, C, generator=g) / C ** 0.5, torch.randn(Hh, generator=g)
+    W2, b2 = torch.randn(C, Hh, generator=g) / Hh ** 0.5, torch.randn(C, generator=g)
+    resid = torch.randn(M, C, generator=g)
+    lw, lb = torch.randn(C, generator=g) * 0.1 + 1, torch.randn(C, generator=g) * 0.1
+    y = _ln64(a, lw, lb) if ln else a.double()
+    want = resid.double() + torch.relu(y @ W1.double().t() + b1.double()) @ W2.double().t() + b2.double()
+
+    def make(lay):
+        c = Call(f"cg_ffn_fwd_f32[{lay} M {M} ln {int(ln)} out = resid]")
+        ab = c.cin("a", box(M, C, F32, lay, 0 if ln and lay == "P" else 1), a)       # the header: lda == C with the LayerNorm
+        w1b, w2b = c.cin("w1", box(Hh, C, F32, lay, 2), W1), c.cin("w2", box(C, Hh, F32, lay, 3), W2)
+        b1b, b2b = c.cin("b1", vec(Hh, F32, lay), b1), c.cin("b2", vec(C, F32, lay), b2)
+        lwb = c.cin("ln_w", vec(C, F32, lay), lw) if ln else None
+        lbb = c.cin("ln_b", vec(C, F32, lay), lb) if ln else None
+        ob = c.cio("out = resid", box(M, C, F32, lay, 4), resid)
+        c.launch = lambda: lib().cg_ffn_fwd_f32(M, C, Hh, P(ab), ab.ld, P(lwb), P(lbb), 1e-5, P(w1b), w1b.ld, P(b1b), P(w2b), w2b.ld,
+                                                P(b2b), P(ob), ob.ld, P(ob), ob.ld, stream())
+        c.verify = lambda c_: _assert(relerr(ob.view, want) < 1e-5, (c_.name, relerr(ob.view, want)))
+        return c
+
+    footprint("cg_ffn_fwd_f32", make)
+    refused(make("O"), "cg_ffn_fwd_f32")
+
+
+def test_decode_qkv_f32():
+    """cg_decode_qkv_f32: qkv an output, the caches in/out (only row len - 1 of every (b, h) changes, to
+    the bits of the qkv row just written); layout O refused (ldx / ldw even, x / W / ln_w / ln_b 8-B aligned)."""
+    B, C, H, Tmax, n = 5, 126, 3, 16, 8
+    Dh = C // H
+    g = torch.Generator().manual_seed(27)
+    x = torch.randn(B, C, generator=g) * 2 + 0.5
+    W = torch.randn(3 * C, C, generator=g) / C ** 0.5
+    lw, lb = torch.randn(C, generator=g) * 0.1 + 1, torch.randn(C, generator=g) * 0.1
+    k0, v0 = torch.randn(B * H * Tmax, Dh, generator=g), torch.randn(B * H * Tmax, Dh, generator=g)
+    want = _ln64(x, lw, lb) @ W.double().t()
+
+    def make(lay):
+        c = Call(f"cg_decode_qkv_f32[{lay}]")
+        xb, wb = c.cin("x", box(B, C, F32, lay, 1), x), c.cin("w", box(3 * C, C, F32, lay, 2), W)
+        lwb, lbb = c.cin("ln_w", vec(C, F32, lay), lw), c.cin("ln_b", vec(C, F32, lay), lb)
+        qb = c.cout("qkv", box(B, 3 * C, F32, lay, 3))
+        kb = c.cio("kcache", Box(B * H * Tmax, Dh, F32, offset_bytes=off(lay, F32), device=DEV), k0)
+        vb = c.cio("vcache", Box(B * H * Tmax, Dh, F32, offset_bytes=off(lay, F32), device=DEV), v0)
+        ln = c.keep = dev_i64(n)
+        c.launch = lambda: lib().cg_decode_qkv_f32(B, C, H, P(xb), xb.ld, P(lwb), P(lbb), 1e-5, P(wb), wb.ld, P(qb), qb.ld, P_t(ln),
+                                                   Tmax, P(kb), P(vb), stream())
+
+        def verify(c_):
+            got = qb.view.cpu()
+            assert relerr(got, want) < 1e-5, (c_.name, relerr(got, want))
+            for name, bx, init, col in (("k", kb, k0, C), ("v", vb, v0, 2 * C)):
+                exp = init.clone().view(B, H, Tmax, Dh)
+                exp[:, :, n - 1] = got[:, col:col + C].reshape(B, H, Dh)
+                assert torch.equal(bx.view.cpu().view(I32), exp.view(-1, Dh).view(I32)), (c_.name, name)
+
+        c.verify = verify
+        return c
+
+    footprint("cg_decode_qkv_f32", make)
+    refused(make("O"), "cg_decode_qkv_f32")
+
+
 # ---- the registry: no entry point left out, nothing skipped silently --------------------------------------
 def strided_entry_points():
-    """Every cg_* function of the header that takes a row-stride argument (ld*, or a problem list)."""
+    """Every cg_* function of the header that takes a stride argument (ld*, stride_*, sb / sh / sj, or a
+    problem list)."""
     src = re.sub(r"/\*.*?\*/", "", open(L().HEADER_PATH).read(), flags=re.S)
     out = set()
     for name, args in re.findall(r"\b(cg_\w+)\s*\(([^;{]*?)\)\s*;", src):
-        if re.search(r"int64_t\s+ld\w*\b", args) or "cg_wgrad_problem_t" in args:
+        if re.search(r"int64_t\s+(ld\w*|stride_\w+|sb|sh|sj)\b", args) or "cg_wgrad_problem_t" in args:
             out.add(name)
     return out
 
 
 def test_every_strided_entry_point_ran_padded():
     """For every entry point of the header that takes a stride, at least one layout-P case ran the
-    kernel (the decode and inference calls have their padded-row tests elsewhere).  Also prints the
+    kernel (the samplers and the two prefill calls have theirs in the files ELSEWHERE names).  Also prints the
     run's record: the case count, every asserted refusal and every check-2 fallback."""
     entries = strided_entry_points()
     assert {"cg_gemm", "cg_attn_bwd_delta", "cg_ce_bwd", "cg_colsum", "cg_head_bwd_ex"} <= entries
-    assert ELSEWHERE <= entries
+    assert ELSEWHERE <= entries and MOVED_HERE <= entries and not (ELSEWHERE & MOVED_HERE)
     need = sorted(e for e in entries - ELSEWHERE if not e.endswith("_supported"))
     print(f"\nfootprint cases run: {CASES[0]}")
     print(f"layout-P runs per strided entry point: { {e: RAN_P.get(e, 0) for e in need} }")
@@ -1222,5 +1462,6 @@ def test_every_strided_entry_point_ran_padded():
     print("check 2 replaced by check 1:")
     for case, why in sorted(set(FELL_BACK)):
         print(f"  {case}: {why}")
+    assert MOVED_HERE <= set(need)
     missing = [e for e in need if RAN_P.get(e, 0) == 0]
     assert not missing, f"no layout-P case ran {missing}"

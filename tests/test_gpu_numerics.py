@@ -1,4 +1,5 @@
-"""The training kernels on ill-scaled data, judged element by element (tests/numerics.py), on the MI355X.
+"""The training and the inference kernels on ill-scaled data, judged element by element (tests/numerics.py),
+on the MI355X.
 
 BUDGET TESTS.  Every case runs a kernel on a data profile, computes rho_kernel = max |got - ref| / (u S)
 against the fp64 reference and the element-wise budget S, and asserts rho_kernel <= 8 rho_plain, with
@@ -12,6 +13,12 @@ with the operand times 2^-24 and 2^+24.
 
 ADAMW AT THE EDGES.  cg_adamw / _segments / _dyn against the numpy restatement of csrc/adamw.h on
 zero, subnormal, tiny, huge and overflowing moments, bit for bit.
+
+THE INFERENCE KERNELS (decode.hip, rows_f32.hip) have the same three kinds of case at u = 2^-24: the decode
+attention's online softmax over 64-key chunks in every dispatch form and the one-pass prefill, with the
+stale cache rows NaN in one run and zero in another; the log-probabilities of cg_decode_logprob_rows and
+cg_decode_emit (no operand to scale: the two must agree bit for bit instead); the fp32 Linear / QKV / FFN
+rows with and without their LayerNorm.
 
 Every case appends a line to RECORDS; the last tests check that every kernel family saw a non-unit
 profile and a scaling case, and write the table to the file CHARPT_NUMERICS_REPORT names (the
@@ -36,10 +43,14 @@ NAN = float("nan")
 
 FAMILIES = ["GEMM bf16", "GEMM fp32", "grouped wgrad", "GEMM + LayerNorm", "LayerNorm forward", "LayerNorm backward",
             "attention D = 64 resident", "attention ring", "attention generic", "attention fp32", "cross entropy",
-            "head", "embedding", "reductions"]
+            "head", "embedding", "reductions", "decode attention", "inference rows", "log-probabilities"]
+# Families with no operand they are linear in: their exact check is a bit equality (Checks.same) instead.
+# Keep this to the log-probabilities (log softmax is linear in nothing): a family whose kernels are linear
+# in an operand belongs to the scaling rule, and an entry here exempts it from that rule.
+NONLINEAR = {"log-probabilities"}
 RECORDS = []     # budget lines: (family, kernel, shape, profile, output, rho_plain, rho_kernel, cap)
 SCALINGS = []    # (family, kernel, what, k, "bitwise")
-SEEN = {f: {"profiles": set(), "scaling": 0} for f in FAMILIES}
+SEEN = {f: {"profiles": set(), "scaling": 0, "same": 0} for f in FAMILIES}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -138,6 +149,7 @@ class Checks:
             self.bad.append(f"{kernel} {what} x 2^{k}: {msg}")
 
     def same(self, kernel, what, a, b):
+        SEEN[self.family]["same"] += 1
         if not torch.equal(a.cpu(), b.cpu()):
             self.bad.append(f"{kernel} {what}: bits differ")
 
@@ -1036,15 +1048,349 @@ def test_adamw_edges(form, step):
     assert not bad, f"cg_adamw {form} step {step}:\n" + "\n".join(bad)
 
 
+# ==== the inference kernels: decode attention ================================================================
+DEC_B, DEC_T, DEC_H = 2, 130, 2
+DEC_PROFILES = ["unit", "peaked", "sink", "shifted", "spiked"]
+DEC_NS = (1, 64, 65, 130)
+# form -> (D, Tmax of the cache or None for a window's qkv rows, decode_attn_rows tuning, the kernel it reaches)
+DEC_FORMS = {
+    "cache130-D21": (21, 130, 1, "k_decode_attn_rows<24,SJ> (sh = 130 x 21 is no multiple of 4)"),
+    "cache132-D21": (21, 132, 1, "k_decode_attn_rows<24>"),
+    "qkvrows-D21": (21, None, 1, "k_decode_attn_rows<24,SJ>"),
+    "generic-D21": (21, 130, 0, "k_decode_attn<24>"),
+    "cache130-D64": (64, 130, 1, "k_decode_attn<64>"),
+}
+_DEC_CACHE = {}
+
+
+def decode_case(D_, profile):
+    """Operands (fp32 values), the budget of o and the per-row rho_plain, computed once per (D, profile)."""
+    key = (D_, profile)
+    if key not in _DEC_CACHE:
+        q, k, v, scale = nm.attn_operands(gen(5), DEC_B, DEC_T, DEC_H, D_, profile)
+        q, k, v = (nm.rnd(t, F32) for t in (q, k, v))
+        scale = float(np.float32(scale))
+        ref, S = nm.attn_budget(q, k, v, torch.zeros_like(q), scale, fp32_cond=True)["o"]
+        _DEC_CACHE[key] = (q, k, v, scale, ref, S, nm.decode_attn_rho_plain(q, k, v, scale, ref, S))
+    return _DEC_CACHE[key]
+
+
+def run_decode_attn(form, q, k, v, n, scale, stale=NAN, fixed=False):
+    """cg_decode_attn for the query at position n - 1 against keys 0..n-1 in the layout of `form`; the key
+    rows >= n hold `stale`.  Returns o [B, H, D] on the CPU."""
+    D_, Tmax, _, _ = DEC_FORMS[form]
+    B, T, H, _ = q.shape
+    HD = H * D_
+    qd = D(q[:, n - 1].reshape(B, HD))
+    o = torch.full((B, HD), NAN, device=DEV)
+    if Tmax is None:
+        buf = torch.cat([t.reshape(B, T, HD) for t in (q, k, v)], 2).clone()
+        buf[:, n:, HD:] = stale
+        bufd = D(buf)
+        kp, vp, sb, sh, sj = P(bufd, HD), P(bufd, 2 * HD), T * 3 * HD, D_, 3 * HD
+    else:
+        kc = torch.full((B, H, Tmax, D_), stale)
+        vc = torch.full((B, H, Tmax, D_), stale)
+        kc[:, :, :n], vc[:, :, :n] = k[:, :n].permute(0, 2, 1, 3), v[:, :n].permute(0, 2, 1, 3)
+        kd, vd = D(kc), D(vc)
+        kp, vp, sb, sh, sj = P(kd), P(vd), H * Tmax * D_, Tmax * D_, D_
+    ln = None if fixed else dev_i64(n)
+    ok(lib().cg_decode_attn(P(qd), HD, kp, vp, sb, sh, sj, B, H, D_, P(ln), n if fixed else 0, scale, P(o), HD, stream()),
+       f"cg_decode_attn {form} n {n}")
+    return o.cpu().view(B, H, D_)
+
+
+@pytest.mark.parametrize("profile", DEC_PROFILES)
+@pytest.mark.parametrize("form", list(DEC_FORMS))
+def test_decode_attn_budget(form, profile):
+    """cg_decode_attn at n in {1, 64, 65, 130} keys in every dispatch form, the cache rows past n NaN in one
+    run and zero in another (both with a device length): finite, bitwise equal, and inside 8 rho_plain of
+    row n - 1; a third run with the key count as an argument gives the same bits."""
+    D_, Tmax, rows_tuning, kernel = DEC_FORMS[form]
+    q, k, v, scale, ref, S, rp = decode_case(D_, profile)
+    ck = Checks("decode attention")
+    assert tuning("decode_attn_rows", rows_tuning) == 0
+    try:
+        for n in DEC_NS:
+            got = run_decode_attn(form, q, k, v, n, scale, NAN)
+            ck.require(bool(torch.isfinite(got).all()), f"cg_decode_attn {form} n {n} {profile}: non-finite output over NaN stale rows")
+            ck.same("cg_decode_attn", f"{form} n {n} {profile}: NaN against zero stale rows (len_dev)", got,
+                    run_decode_attn(form, q, k, v, n, scale, 0.0))
+            ck.same("cg_decode_attn", f"{form} n {n} {profile}: a fixed nkeys against len_dev (NaN stale rows)", got,
+                    run_decode_attn(form, q, k, v, n, scale, NAN, fixed=True))
+            ck.budget(f"cg_decode_attn {kernel.split(' ')[0]}", f"({DEC_B}, {DEC_H}, {D_}) {form} n {n}", profile, "o", got,
+                      ref[:, n - 1], S[:, n - 1], U32, float(rp[n - 1]))
+    finally:
+        tuning("decode_attn_rows", 1)
+    ck.done()
+
+
+def run_prefill_attn(q, k, v, scale, Tmax):
+    """cg_decode_prefill_attn over all P = T positions from a qkv row buffer.  Returns o [B, T, H, D], kc, vc."""
+    B, T, H, D_ = q.shape
+    HD = H * D_
+    buf = D(torch.cat([t.reshape(B * T, HD) for t in (q, k, v)], 1))
+    kc = torch.full((B, H, Tmax, D_), NAN, device=DEV)
+    vc = torch.full((B, H, Tmax, D_), NAN, device=DEV)
+    o = torch.full((B * T, HD), NAN, device=DEV)
+    ok(lib().cg_decode_prefill_attn(P(buf), 3 * HD, P(buf, HD), P(buf, 2 * HD), 3 * HD, B, T, H, D_, Tmax, scale, P(kc), P(vc),
+                                    P(o), HD, stream()), "cg_decode_prefill_attn")
+    return o.cpu().view(B, T, H, D_), kc.cpu(), vc.cpu()
+
+
+@pytest.mark.parametrize("profile", DEC_PROFILES)
+@pytest.mark.parametrize("D_", [21, 64])
+def test_decode_prefill_attn_budget(D_, profile):
+    """cg_decode_prefill_attn with P = 130 (QB 8 at D 21, QB 4 at D 64): the whole o against every row of
+    the budget; the cache rows are exact copies and the rows past P stay untouched."""
+    q, k, v, scale, ref, S, rp = decode_case(D_, profile)
+    ck = Checks("decode attention")
+    Tmax = DEC_T + 2
+    o, kc, vc = run_prefill_attn(q, k, v, scale, Tmax)
+    ck.budget(f"cg_decode_prefill_attn QB {8 if D_ <= 24 else 4}", f"({DEC_B}, {DEC_T}, {DEC_H}, {D_})", profile, "o", o, ref, S, U32,
+              float(rp.max()))
+    ck.same("cg_decode_prefill_attn", "k cache rows", kc[:, :, :DEC_T], k.permute(0, 2, 1, 3).float())
+    ck.same("cg_decode_prefill_attn", "v cache rows", vc[:, :, :DEC_T], v.permute(0, 2, 1, 3).float())
+    ck.require(bool(torch.isnan(kc[:, :, DEC_T:]).all() and torch.isnan(vc[:, :, DEC_T:]).all()), "cache rows past P written")
+    ck.done()
+
+
+@pytest.mark.parametrize("form", list(DEC_FORMS) + ["prefill-D21", "prefill-D64"])
+def test_decode_attn_scaling(form):
+    """o scales bit for bit in v (2^-24, 2^24) and keeps its bits under q 2^k with scale 2^-k."""
+    ck = Checks("decode attention")
+    prefill = form.startswith("prefill")
+    D_ = int(form.split("-D")[1])
+    q, k, v, scale, _, _, _ = decode_case(D_, "unit")
+    assert tuning("decode_attn_rows", 1 if prefill else DEC_FORMS[form][2]) == 0
+
+    def run(q_, v_, sc, n):
+        return run_prefill_attn(q_, k, v_, sc, DEC_T)[0] if prefill else run_decode_attn(form, q_, k, v_, n, sc, 0.0)
+
+    try:
+        for n in ((DEC_T,) if prefill else (65, 130)):
+            base = run(q, v, scale, n)
+            for e in (-24, 24):
+                f = 2.0 ** e
+                ck.scaling("cg_decode_prefill_attn" if prefill else "cg_decode_attn", f"{form} n {n} o in v", base, run(q, v * f, scale, n), e)
+                ck.scaling("cg_decode_prefill_attn" if prefill else "cg_decode_attn", f"{form} n {n} o under q 2^{e}, scale 2^{-e}", base,
+                           run(q * f, v, scale / f, n), 0)
+    finally:
+        tuning("decode_attn_rows", 1)
+    ck.done()
+
+
+# ==== the inference kernels: log-probabilities ==============================================================
+def run_logprob_rows(x, tgt, B, P_):
+    """cg_decode_logprob_rows on rows b P + t of x with idx[b, t + 1] = tgt; returns the B P values."""
+    V = x.shape[1]
+    idx = torch.zeros(B, P_ + 1, dtype=I64)
+    idx[:, 1:] = tgt.view(B, P_)
+    xd, ixd = D(x), D(idx)
+    lp = torch.full((B, P_ + 1), NAN, device=DEV)
+    ok(lib().cg_decode_logprob_rows(P(xd), V, V, B, P_, P(ixd), P_ + 1, P(lp), P_ + 1, stream()), "cg_decode_logprob_rows")
+    lp = lp.cpu()
+    assert bool(torch.isnan(lp[:, 0]).all()), "cg_decode_logprob_rows wrote column 0"
+    return lp[:, 1:].reshape(-1)
+
+
+def run_emit_logprob(x, tgt):
+    """Step 4 of cg_decode_emit with forced tokens (n = 3 < prompt_len = 5): the token is the target."""
+    rows, V = x.shape
+    n, ld = 3, 8
+    idx = torch.zeros(rows, ld, dtype=I64)
+    idx[:, n] = tgt
+    xd, ixd = D(x), D(idx)
+    lp = torch.full((rows, ld), NAN, device=DEV)
+    plen, lim, end = (torch.full((rows,), val, dtype=I64, device=DEV) for val in (5, 100, 0))
+    stop = torch.zeros((V + 63) // 64, dtype=I64, device=DEV)
+    pad, ln = dev_i64(0), dev_i64(n)
+    ok(lib().cg_decode_emit(P(xd), V, V, rows, 0, None, None, P(ln), P(plen), P(lim), P(end), P(stop), P(pad), P(ixd), ld, P(lp),
+                            stream()), "cg_decode_emit")
+    assert torch.equal(ixd.cpu(), idx) and int(end.abs().sum()) == 0, "cg_decode_emit wrote a forced row's token or ended it"
+    return lp.cpu()[:, n]
+
+
+@pytest.mark.parametrize("profile", ["unit", "confident", "wrong", "offset", "certain"])
+@pytest.mark.parametrize("V", [65, 200])
+def test_logprob_budget(V, profile):
+    """cg_decode_logprob_rows and cg_decode_emit's step 4 on 64 rows: inside the shift-invariant budget,
+    and equal to each other bit for bit on every profile."""
+    rows = 64
+    ck = Checks("log-probabilities")
+    x, tgt = nm.ce_logits(gen(900 + V), rows, V, profile)
+    ref, S = nm.logprob_budget(x, tgt)
+    rp = nm.logprob_rho_plain(x, tgt, ref, S)
+    a, b = run_logprob_rows(x, tgt, 4, 16), run_emit_logprob(x, tgt)
+    ck.budget("cg_decode_logprob_rows", (rows, V), profile, "logprob", a, ref, S, U32, rp)
+    ck.budget("cg_decode_emit step 4", (rows, V), profile, "logprob", b, ref, S, U32, rp)
+    ck.same("cg_decode_emit / cg_decode_logprob_rows", f"({rows}, {V}) {profile}", a, b)
+    ck.done()
+
+
+# ==== the inference kernels: rows_f32.hip ===================================================================
+def run_linear_rows(a, lw, lb, W, bias=None, relu=False, resid=None):
+    M, K = a.shape
+    N = W.shape[0]
+    ad, lwd, lbd, wd, bd, rd = D(a), D(lw), D(lb), D(W), D(bias), D(resid)
+    out = torch.full((M, N), NAN, device=DEV)
+    ok(lib().cg_linear_rows_f32(M, N, K, P(ad), K, P(lwd), P(lbd), nm.EPS, P(wd), K, P(bd), int(relu), P(rd), N, P(out), N, stream()),
+       f"cg_linear_rows_f32 {M}x{N}x{K}")
+    return out.cpu()
+
+
+ROW_KINDS = {"store": {}, "bias": dict(bias=True), "bias_relu": dict(bias=True, relu=True), "bias_resid": dict(bias=True, resid=True)}
+
+
+def row_epilogue(kind, bias, resid, f=1.0):
+    kw = ROW_KINDS[kind]
+    return dict(bias=bias * f if kw.get("bias") else None, relu=bool(kw.get("relu")), resid=resid * f if kw.get("resid") else None)
+
+
+@pytest.mark.parametrize("profile", ["offset", "flat", "scaling"])
+@pytest.mark.parametrize("K", [126, 128])
+def test_linear_rows_f32_ln_small(K, profile):
+    """cg_linear_rows_f32 with the LayerNorm at M 33 (the <= 2048-row path through k_gemm_f32r), every
+    epilogue kind; profile "scaling": linear in (W, bias) with the residual scaled along."""
+    M, N = 33, 70
+    ck = Checks("inference rows")
+    g = gen(560 + K)
+    a = nm.ln_rows(g, M, K, "unit" if profile == "scaling" else profile)
+    lw, lb = nm.ln_params(g, K)
+    W, bias, resid = torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g), torch.randn(M, N, generator=g)
+    for kind in ROW_KINDS:
+        e = row_epilogue(kind, bias, resid)
+        got = run_linear_rows(a, lw, lb, W, **e)
+        if profile == "scaling":
+            for k in (-24, 24):
+                f = 2.0 ** k
+                ck.scaling("cg_linear_rows_f32 ln", f"({M}, {N}, {K}) {kind} in (W, bias, resid)", got,
+                           run_linear_rows(a, lw, lb, W * f, **row_epilogue(kind, bias, resid, f)), k)
+        else:
+            ref, S = nm.linear_ln_budget(a, lw, lb, W, **e)
+            ck.budget("cg_linear_rows_f32 ln", f"({M}, {N}, {K}) {kind}", profile, "out", got, ref, S, U32,
+                      nm.linear_ln_rho_plain(a, lw, lb, W, ref, S, **e))
+    ck.done()
+
+
+@pytest.mark.parametrize("profile", ["outlier", "scaling"])
+@pytest.mark.parametrize("M,nb", [(33, 0), (2050, 0), (2050, 1), (2050, 2)])
+def test_linear_rows_f32_plain(M, nb, profile):
+    """cg_linear_rows_f32 without the LayerNorm on outlier operands: M 33, and M 2050 under every
+    linear_rows_nb tuning (k_linear_f32q, k_linear_f32t<1>, <2>); "scaling": linear in a (bias, resid along)."""
+    N, K = 70, 126
+    ck = Checks("inference rows")
+    g = gen(570 + M)
+    a, W, _ = nm.gemm_operands(g, M, N, K, "unit" if profile == "scaling" else profile, F32)
+    bias, resid = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
+    assert tuning("linear_rows_nb", nb) == 0
+    try:
+        for kind in ROW_KINDS:
+            e = row_epilogue(kind, bias, resid)
+            got = run_linear_rows(a, None, None, W, **e)
+            name = f"cg_linear_rows_f32 nb {nb}"
+            if profile == "scaling":
+                for k in (-24, 24):
+                    f = 2.0 ** k
+                    ck.scaling(name, f"({M}, {N}, {K}) {kind} in (a, bias, resid)", got,
+                               run_linear_rows(a * f, None, None, W, **row_epilogue(kind, bias, resid, f)), k)
+            else:
+                ref, S = nm.linear_ln_budget(a, None, None, W, **e)
+                ck.budget(name, f"({M}, {N}, {K}) {kind}", profile, "out", got, ref, S, U32,
+                          nm.linear_ln_rho_plain(a, None, None, W, ref, S, **e), nm.dot_cap(K, 3))
+    finally:
+        tuning("linear_rows_nb", 0)
+    ck.done()
+
+
+@pytest.mark.parametrize("profile", ["offset", "flat", "scaling"])
+def test_decode_qkv_f32(profile):
+    """cg_decode_qkv_f32 at B 33, C 126, H 6, Tmax 16, position 7: qkv inside the LayerNorm + product
+    budget, the appended cache rows exact copies of it, every other cache row untouched."""
+    B, C, H, Tmax, pos = 33, 126, 6, 16, 7
+    Dh = C // H
+    ck = Checks("inference rows")
+    g = gen(580)
+    x = nm.ln_rows(g, B, C, "unit" if profile == "scaling" else profile)
+    lw, lb = nm.ln_params(g, C)
+    W = torch.randn(3 * C, C, generator=g) / C ** 0.5
+
+    def run(Wx):
+        xd, lwd, lbd, wd = D(x), D(lw), D(lb), D(Wx)
+        qkv = torch.full((B, 3 * C), NAN, device=DEV)
+        kc, vc = torch.full((B, H, Tmax, Dh), NAN, device=DEV), torch.full((B, H, Tmax, Dh), NAN, device=DEV)
+        ln = dev_i64(pos + 1)
+        ok(lib().cg_decode_qkv_f32(B, C, H, P(xd), C, P(lwd), P(lbd), nm.EPS, P(wd), C, P(qkv), 3 * C, P(ln), Tmax, P(kc), P(vc),
+                                   stream()), "cg_decode_qkv_f32")
+        return qkv.cpu(), kc.cpu(), vc.cpu()
+
+    qkv, kc, vc = run(W)
+    for name, cache, off in (("k", kc, C), ("v", vc, 2 * C)):
+        ck.same("cg_decode_qkv_f32", f"{name} cache row {pos}", cache[:, :, pos], qkv[:, off:off + C].reshape(B, H, Dh))
+        rest = torch.cat([cache[:, :, :pos], cache[:, :, pos + 1:]], 2)
+        ck.require(bool(torch.isnan(rest).all()), f"cg_decode_qkv_f32 wrote {name} cache rows other than {pos}")
+    if profile == "scaling":
+        for k in (-24, 24):
+            q2, kc2, vc2 = run(W * 2.0 ** k)
+            ck.scaling("cg_decode_qkv_f32", f"({B}, {C}, {H}) qkv in W", qkv, q2, k)
+            ck.scaling("cg_decode_qkv_f32", f"({B}, {C}, {H}) k cache row in W", kc[:, :, pos], kc2[:, :, pos], k)
+    else:
+        ref, S = nm.linear_ln_budget(x, lw, lb, W)
+        ck.budget("cg_decode_qkv_f32", (B, C, H), profile, "qkv", qkv, ref, S, U32, nm.linear_ln_rho_plain(x, lw, lb, W, ref, S))
+    ck.done()
+
+
+@pytest.mark.parametrize("profile", ["hard", "scaling"])
+@pytest.mark.parametrize("ln", [True, False], ids=["ln", "noln"])
+@pytest.mark.parametrize("M", [33, 2050])
+def test_ffn_fwd_f32(M, ln, profile):
+    """cg_ffn_fwd_f32 at C 126, H 504: with the LayerNorm on offset and flat rows, without it on outlier
+    operands; "scaling": linear in (W2, b2, resid)."""
+    C, Hh = 126, 504
+    assert lib().cg_ffn_fwd_f32_supported(M, C, Hh)
+    ck = Checks("inference rows")
+    for prof in (("unit",) if profile == "scaling" else (("offset", "flat") if ln else ("outlier",))):
+        g = gen(590 + M)
+        if ln:
+            a = nm.ln_rows(g, M, C, prof)
+            W1 = torch.randn(Hh, C, generator=g) / C ** 0.5
+            lw, lb = nm.ln_params(g, C)
+        else:
+            a, W1, _ = nm.gemm_operands(g, M, Hh, C, prof, F32)
+            lw = lb = None
+        b1, b2 = torch.randn(Hh, generator=g), torch.randn(C, generator=g)
+        W2, resid = torch.randn(C, Hh, generator=g) / Hh ** 0.5, torch.randn(M, C, generator=g)
+
+        def run(f=1.0):
+            ad, lwd, lbd, w1d, b1d, w2d, b2d, rd = (D(t) for t in (a, lw, lb, W1, b1, W2 * f, b2 * f, resid * f))
+            out = torch.full((M, C), NAN, device=DEV)
+            ok(lib().cg_ffn_fwd_f32(M, C, Hh, P(ad), C, P(lwd), P(lbd), nm.EPS, P(w1d), C, P(b1d), P(w2d), Hh, P(b2d), P(rd), C, P(out),
+                                    C, stream()), "cg_ffn_fwd_f32")
+            return out.cpu()
+
+        got = run()
+        shape = f"({M}, {C}, {Hh}) ln {int(ln)}"
+        if profile == "scaling":
+            for k in (-24, 24):
+                ck.scaling("cg_ffn_fwd_f32", f"{shape} in (W2, b2, resid)", got, run(2.0 ** k), k)
+        else:
+            ref, S = nm.ffn_budget(a, lw, lb, W1, b1, W2, b2, resid)
+            ck.budget("cg_ffn_fwd_f32", shape, prof, "out", got, ref, S, U32, nm.ffn_rho_plain(a, lw, lb, W1, b1, W2, b2, resid, ref, S))
+    ck.done()
+
+
 # ==== the record ==============================================================================================
 def test_every_family_saw_a_hard_profile_and_a_scaling_case():
     """Run last (pytest keeps the file's order): each kernel family has at least one budget case on a
-    non-unit profile and one exact-scaling case."""
+    non-unit profile and one exact-scaling case (a family in NONLINEAR: one bit-equality case)."""
     missing = []
     for fam in FAMILIES:
         if not SEEN[fam]["profiles"] - {"unit"}:
             missing.append(f"{fam}: no budget case on a non-unit profile")
-        if SEEN[fam]["scaling"] == 0:
+        if fam in NONLINEAR:
+            if SEEN[fam]["same"] == 0:
+                missing.append(f"{fam}: no bit-equality case")
+        elif SEEN[fam]["scaling"] == 0:
             missing.append(f"{fam}: no exact-scaling case")
     assert not missing, "\n".join(missing)
 

@@ -117,6 +117,48 @@ def test_filtered_matches_fp64_contract(Vn, scale):
             assert share <= 0.03, f"V={Vn} scale={scale} ({tau},{k},{p}) len={length}: {100 * share:.2f} % gated (cap 3 %)"
 
 
+ILL_SETTINGS = [(0.05, 0, 1.0), (20.0, 0, 0.9), (1.0, 0, 0.9), (0.05, 5, 0.5), (20.0, 40, 0.95)]
+
+
+def ill_scaled_logits(profile, Bn=1024, Vn=V):
+    """1024 rows of 3 * randn at V 65: as they are ("unit"), every logit + 1e3 ("offset": the fp32
+    logits lose 13 bits below the point, the differences against the row maximum stay exact), or one
+    column per row raised 30 above the row maximum ("raised": at tau 0.05 every other weight is
+    exp(-600 or less) = 0, at tau 20 the raised column has a fifth of the weight of its row)."""
+    gen = torch.Generator().manual_seed(4242)
+    x = 3 * torch.randn(Bn, Vn, generator=gen)
+    if profile == "offset":
+        x = x + 1e3
+    elif profile == "raised":
+        col = torch.randint(0, Vn, (Bn,), generator=gen)
+        x[torch.arange(Bn), col] = x.max(1).values + 30
+    elif profile != "unit":
+        raise ValueError(profile)
+    return x
+
+
+@pytest.mark.parametrize("profile", ["unit", "offset", "raised"])
+def test_filtered_on_ill_scaled_logits(profile):
+    """A sharp and a flat temperature (0.05, 20) with and without the cuts, on logits far from zero and
+    on rows with one dominant column: every ungated row draws the reference's token; at most 3 % of a
+    case's rows are gated (the reference alone gates at most 1.3 % of these on the CPU)."""
+    logits = ill_scaled_logits(profile)
+    lg = logits.to(DEV)
+    g = filtered_gate(V)
+    length, seed = 37, 987654321
+    for tau, k, p in ILL_SETTINGS:
+        ref = reference(logits, tau, k, p, seed, length, g)
+        want, gated = ref["tok"], ref["gated"]
+        share = float(gated.mean())
+        tok = run_filtered(lg, (tau, k, p), seed, length)
+        miss = (tok != want) & ~gated
+        print(f"{profile} (t,k,p)=({tau},{k},{p}): gated {100 * share:.2f} %, gated rows differing "
+              f"{int(((tok != want) & gated).sum())}, ungated mismatches {int(miss.sum())}")
+        assert not miss.any(), (profile, tau, k, p, int(miss.sum()), int(np.nonzero(miss)[0][0]))
+        assert bool(ref["kept"][np.arange(len(tok)), tok][~gated].all())
+        assert share <= 0.03, f"{profile} ({tau},{k},{p}): {100 * share:.2f} % gated (cap 3 %)"
+
+
 # ---------------------------------------------------------------------------------------
 # 3. degenerate settings are greedy
 # ---------------------------------------------------------------------------------------
